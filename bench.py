@@ -6,6 +6,13 @@ Reddit-shaped by default) graph, inputs resident in HBM.  Prints ONE JSON
 line on rank 0 (contract in the task statement / DESIGN.md "Measurement").
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--graph reddit] [--k 32] [--h 256]
+                  [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the headline line.
+--full adds everything else the line can carry (per-call times and roofline,
+parity check of the timed outputs, producer / scatter / autograd / training-step
+times, vendor and CPU baselines, the BASELINE config sweep).  --dump-outputs DIR
+writes the outputs of the last timed step (y, dx) as DIR/<name>.npy.
 
 N>1: launched by torch.distributed.run, one rank per GPU; the graph is 1-D
 row-partitioned (nnz-balanced) and halo CBSR rows / dXs partial sums move with
@@ -72,7 +79,49 @@ def parse():
     p.add_argument("--config-steps", type=int, default=20,
                    help="timed steps per config entry (at least 20 by default; fewer only for "
                         "rehearsals of the plumbing)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="after the headline also measure and check everything else: per-call "
+                        "times and the roofline, the parity check of the timed outputs, top-k / "
+                        "scatter / autograd / training-step times, the vendor and CPU baselines "
+                        "and the BASELINE config sweep (a plain run times the steps only)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the last one returned (rank 0's rows "
+                        "at N > 1) as DIR/<name>.npy; a fixed seeded row sample when larger than "
+                        "the dump budget")
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+# all arrays of one --dump-outputs together (the .npy files stay below 64 MB)
+DUMP_BUDGET_BYTES = 48 << 20
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write the arrays a caller of the timed path receives as <out_dir>/<name>.npy
+    (float32, or float64 where the path computes in it).  Each array gets an equal
+    share of `budget`; a larger one is cut to a sorted row sample drawn with a fixed
+    seed from its shape alone (rows = all leading dimensions flattened), so two
+    builds run with the same arguments write the same rows."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget // max(len(arrays), 1)
+    written = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.float()
+        rows = t.reshape(-1, t.shape[-1]) if t.dim() > 1 else t.reshape(-1, 1)
+        keep = max(1, share // (rows.shape[1] * rows.element_size()))
+        if keep < rows.shape[0]:
+            idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], size=keep, replace=False))
+            t = rows.index_select(0, torch.from_numpy(idx).to(rows.device))
+        a = t.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = a.shape
+    log(f"[bench] outputs of the last timed step written to {out_dir}: {written}")
+    return written
 
 
 @contextlib.contextmanager
@@ -427,7 +476,14 @@ def bench_multi_partitioned(args, indptr, indices, vals, data, sel, V, E, h, k, 
         return float(tt) / args.steps * 1e3
     model.forward_multi(data_l, sel_l, h)   # plans, workspaces, AUTO choice
     model.backward_multi(G_l, sel_l)
-    t_f = timed(lambda: model.forward_multi(data_l, sel_l, h))
+    last = {}
+
+    def fused():
+        last["y"] = model.forward_multi(data_l, sel_l, h)
+    t_f = timed(fused)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
+    last.clear()
     t_b = timed(lambda: model.backward_multi(G_l, sel_l))
     val = b_fused / (t_f / 1e3) / 1e9
     b_rank = torch.tensor([float(model.algorithmic_bytes_multi(k, h))], device=dev,
@@ -938,7 +994,10 @@ def bench_multi(args, S, indptr, indices, data, sel, V, E, h, k, dev, world, ran
     fused()
     unfused()
     backward()  # plans, workspaces and the AUTO choice before any timing
-    t_f, t_u = timed(fused), timed(unfused)
+    t_f = timed(fused)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"y": y})
+    t_u = timed(unfused)
     t_b = timed(backward)
     b_unf = R * (8 * E + 5 * k * E + 4 * h * V)
     val = b_fused / (t_f / 1e3) / 1e9
@@ -1141,6 +1200,7 @@ def main():
         def step():
             fwd_call()
             bwd_call()
+            return y, dx
 
     for _ in range(args.warmup):
         step()
@@ -1150,7 +1210,7 @@ def main():
     torch.cuda.synchronize()
     t_start = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     if dist:
         dist.barrier()
@@ -1175,6 +1235,11 @@ def main():
                    "bwd_algo": args.bwd_algo, "auto_mode": os.environ.get("MAXK_AUTO")},
     }
 
+    if args.dump_outputs and rank == 0:
+        # what the last timed step returned (at N > 1: rank 0's own rows)
+        dump_outputs(args.dump_outputs, {"y": last[0], "dx": last[1]})
+    del last
+
     if partitioned:
         p = model.plan
         result["config"]["halo_nodes_rank0"] = p.num_halo
@@ -1183,6 +1248,10 @@ def main():
         # the all-gather table path exists only with the own | halo split
         result["config"]["halo_mode"] = model.halo_mode if model.overlap else "records"
         result["config"]["halo_bytes_rank0"] = model.halo_bytes(k)
+    else:
+        result["config"]["bwd_algo"] = g.last_bwd_algo
+    # everything below measures or checks more than the headline: only with --full
+    if partitioned and args.full:
         # per-call timing on each rank (HIP events on the launch stream; the
         # calls include their halo all-to-all-v), max over ranks
         st = torch.cuda.current_stream()
@@ -1238,7 +1307,7 @@ def main():
             del model, data_l, sel_l, G_l, X, G, data, sel, indices, values
             torch.cuda.empty_cache()
             result["configs"] = partitioned_configs(args, dev, world, rank, dist, kw)
-    if not partitioned:
+    if not partitioned and args.full:
         # per-call timing with HIP events on the launch stream (the current stream)
         st = torch.cuda.current_stream()
         fw, bw = [], []

@@ -15,7 +15,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.parametrize("extra", [[], ["--partitioned"], ["--graph", "proteins", "--relations", "4"]])
 def test_bench_json_line(extra):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--graph", "flickr", "--h", "64",
-           "--k", "16", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1", "--no-vendor"] + extra
+           "--k", "16", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1", "--no-vendor",
+           "--full"] + extra
     if "--relations" in extra:
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
                "--k", "32"] + extra
@@ -41,6 +42,38 @@ def test_bench_json_line(extra):
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run (no --full) times the steps only: its line carries the headline
+    fields and none of the extra measurements; --dump-outputs writes the y and dx
+    of the last timed step whole (flickr fits the dump budget): float32, finite,
+    non-negative and not all zero (values, X and G are drawn from [0, 1))."""
+    import numpy as np
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--graph", "flickr",
+           "--h", "64", "--k", "16", "--steps", "3", "--warmup", "1",
+           "--dump-outputs", str(tmp_path / "out")]
+    out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = out.stdout.strip().splitlines()
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
+                "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
+        assert key in d, key
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["unit"] == "GB/s" and d["higher_is_better"] is True and d["dtype"] == "fp32"
+    for key in ("roofline", "bwd_check", "cpu_baseline", "vendor_baseline", "configs",
+                "train_step_ms", "autograd_step_ms", "topk_ms", "copy_GBs", "fwd_ms"):
+        assert key not in d, key
+    v = d["config"]["num_nodes"]
+    y, dx = np.load(tmp_path / "out" / "y.npy"), np.load(tmp_path / "out" / "dx.npy")
+    assert sorted(os.listdir(tmp_path / "out")) == ["dx.npy", "y.npy"]
+    assert y.dtype == np.float32 and dx.dtype == np.float32
+    assert y.shape == (v, 64) and dx.shape == (v, 16)
+    assert np.isfinite(y).all() and np.isfinite(dx).all()
+    assert y.min() >= 0 and dx.min() >= 0 and y.max() > 0 and dx.max() > 0
+
+
+@pytest.mark.gpu
 def test_bench_two_ranks_rehearsal():
     """The N>1 bench path (torch.distributed.run, row partition, halo exchange,
     max-over-ranks timing) end to end with 2 ranks on one GPU; gloo stands in
@@ -49,7 +82,7 @@ def test_bench_two_ranks_rehearsal():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29613", os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--steps", "2", "--warmup", "1", "--graph", "flickr", "--h", "64",
-           "--k", "16", "--overlap", "on"]
+           "--k", "16", "--overlap", "on", "--full"]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads(out.stdout.strip().splitlines()[-1])
@@ -86,7 +119,7 @@ def test_bench_launches_its_own_ranks():
                                                             "MASTER_PORT")}
     env["BENCH_BACKEND"] = "gloo"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--graph", "flickr", "--h", "64", "--k", "16"]
+           "--warmup", "1", "--graph", "flickr", "--h", "64", "--k", "16", "--full"]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = out.stdout.strip().splitlines()
@@ -107,7 +140,7 @@ def test_bench_n2_reports_multi_gpu_configs():
                                                             "MASTER_PORT")}
     env["BENCH_BACKEND"] = "gloo"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--config-steps", "2"]
+           "--warmup", "1", "--config-steps", "2", "--full"]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads(out.stdout.strip().splitlines()[-1])

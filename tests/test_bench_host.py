@@ -84,6 +84,33 @@ def test_median():
     assert bench._median([4.0, 1.0, 2.0, 3.0]) == 2.5
 
 
+def test_dump_outputs_budget_and_fixed_sample(tmp_path):
+    """--dump-outputs: an array within its share of the budget is written whole;
+    a larger one is cut to the same sorted row sample on every call (drawn from the
+    shape alone), leading dimensions flattened; halves and doubles keep a float
+    type; the files together stay within the budget."""
+    import numpy as np
+    import torch
+    small = torch.arange(40 * 8, dtype=torch.float32).reshape(40, 8)
+    big = torch.arange(3 * 500 * 16, dtype=torch.float32).reshape(3, 500, 16)
+    budget = 2 * 100 * 16 * 4          # a share of 100 rows of `big` each
+    for d in ("a", "b"):
+        shapes = bench.dump_outputs(str(tmp_path / d), {"small": small, "big": big},
+                                    budget=budget)
+        assert shapes == {"small": (40, 8), "big": (100, 16)}
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, b)
+    flat = big.reshape(-1, 16).numpy()
+    rows = (a[:, 0] / 16).astype(np.int64)           # row r of `flat` starts at 16 r
+    assert (np.diff(rows) > 0).all() and np.array_equal(a, flat[rows])
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), small.numpy())
+    total = sum(np.load(tmp_path / "a" / f).nbytes for f in os.listdir(tmp_path / "a"))
+    assert total <= budget
+    bench.dump_outputs(str(tmp_path / "c"), {"h": small.half(), "d": small.double()})
+    assert np.load(tmp_path / "c" / "h.npy").dtype == np.float32
+    assert np.load(tmp_path / "c" / "d.npy").dtype == np.float64
+
+
 def test_gpus_beyond_visible_devices_fails_loudly():
     """`bench.py --gpus N` without a launcher starts its own ranks; when N exceeds
     the visible GPUs (none in this container) it exits non-zero before any GPU

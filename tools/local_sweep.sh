@@ -1,9 +1,9 @@
 # LOCAL backward tuning sweep (development helper): prints ms/step and bwd ms per variant
-mkdir -p gpurun_out
+mkdir -p bench_out
 one() {  # one <label> <env...>
     local label=$1; shift
-    env "$@" timeout -k 10 300 python bench.py --bwd-algo local --no-cpu-baseline --steps 10 > gpurun_out/sw.json 2> gpurun_out/sw.err || { tail -5 gpurun_out/sw.err; exit 1; }
-    python -c "import json;d=json.load(open('gpurun_out/sw.json'));print('$label', d['ms_per_step'], d.get('bwd_ms'))"
+    env "$@" timeout -k 10 300 python bench.py --full --bwd-algo local --no-cpu-baseline --steps 10 > bench_out/sw.json 2> bench_out/sw.err || { tail -5 bench_out/sw.err; exit 1; }
+    python -c "import json;d=json.load(open('bench_out/sw.json'));print('$label', d['ms_per_step'], d.get('bwd_ms'))"
 }
 one base MAXK_X=0
 one R32 MAXK_LIB=tools/variants/libR32.so

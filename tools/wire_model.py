@@ -160,22 +160,26 @@ class ThreadFabric:
 
     # ------------------------------------------------------------- plumbing
     def streams_concurrent(self, spin_ms: float = 20.0) -> bool:
-        """Whether every rank's compute stream really runs beside its side stream:
+        """Whether every rank's compute stream really runs beside every side stream:
         HIP maps streams onto a few hardware queues (GPU_MAX_HW_QUEUES), and two
-        streams on one queue run in order -- correct, but not concurrent.  A long
-        spin on the side stream and a tiny op on the compute stream: concurrent when
-        the tiny op completes well before the spin."""
+        streams on one queue run in order -- correct, but not concurrent.  A rank's
+        compute stream behind ANY rank's side stream counts: all deliveries of one
+        collective spin at the same time, so a consumer queued behind a peer's
+        delivery also runs after its own.  A long spin on one side stream and a tiny
+        op on each compute stream: concurrent when every tiny op completes well
+        before the spin, for each side stream in turn."""
         import time
         ok = True
-        for r in range(self.world):
-            with torch.cuda.stream(self.sides[r]):
+        for side in self.sides:
+            with torch.cuda.stream(side):
                 spin_us(spin_ms * 1e3, self.device)
-            done = torch.cuda.Event()
-            with torch.cuda.stream(self.streams[r]):
-                torch.cuda._sleep(1)
-                done.record()
             t0 = time.perf_counter()
-            done.synchronize()
+            for st in self.streams:
+                done = torch.cuda.Event()
+                with torch.cuda.stream(st):
+                    torch.cuda._sleep(1)
+                    done.record()
+                done.synchronize()
             ok = ok and (time.perf_counter() - t0) * 1e3 < spin_ms / 2
             torch.cuda.synchronize(self.device)
         return ok
