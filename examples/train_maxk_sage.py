@@ -12,6 +12,12 @@ the loss can fall).
     python examples/train_maxk_sage.py --graph reddit --steps 20
     python examples/train_maxk_sage.py --graph proteins --relations 8 --steps 20
 
+With --amp bf16 (or fp16, with a GradScaler) the loop runs under torch.autocast
+and the aggregation takes and returns half-precision features (fp32 sums
+inside, one rounding per output element); single relation, one GPU.
+
+    python examples/train_maxk_sage.py --graph reddit --steps 20 --amp bf16
+
 With --relations R the graph carries R edge features (ogbn-proteins has 8) and
 every layer aggregates all of them with one fused SpGEMM (SpGEMMMultiFunction,
 BASELINE config 5) followed by a neighbour weight per relation.
@@ -61,6 +67,10 @@ class MaxKSAGE(nn.Module):
         holds the rank's own rows)."""
         x = self.lin_in(x)
         for layer, norm in zip(self.layers, self.norms):
+            if torch.is_autocast_enabled("cuda"):
+                # LayerNorm returns fp32 under autocast; the aggregation runs in the dtype
+                # of its input, so hand it the autocast dtype
+                x = x.to(torch.get_autocast_dtype("cuda"))
             h = layer(graph, x) if self.num_rel == 1 else layer(graph, x, values)
             x = norm(self.drop(h))
         return self.lin_out(x)
@@ -79,6 +89,9 @@ def main(argv=None):
     p.add_argument("--lr", type=float, default=1e-2)
     p.add_argument("--relations", type=int, default=1,
                    help="R > 1: R edge-feature relations, fused multi-relation aggregation")
+    p.add_argument("--amp", default="off", choices=("off", "bf16", "fp16"),
+                   help="run the loop under torch.autocast: the aggregation then takes and "
+                        "returns bf16 / fp16 features (fp16 with a GradScaler)")
     p.add_argument("--backend", default=os.environ.get("BENCH_BACKEND", "nccl"),
                    help="torch.distributed backend when WORLD_SIZE > 1 (nccl = RCCL)")
     args = p.parse_args(argv)
@@ -99,6 +112,10 @@ def main(argv=None):
         E, V = int(E * args.nodes / V), args.nodes
     indptr, indices = synthetic_csr_gpu(V, E, device=dev)
     R = args.relations
+    amp_dtype = {"off": None, "bf16": torch.bfloat16, "fp16": torch.float16}[args.amp]
+    if amp_dtype is not None and (R > 1 or world > 1):
+        raise SystemExit("--amp: the multi-relation and partitioned aggregations are fp32 only")
+    scaler = torch.amp.GradScaler("cuda", enabled=args.amp == "fp16")
     if R == 1:
         values = torch.ones(indices.numel(), device=dev)      # sum aggregation (utils/models.py:227)
     else:                                                     # R synthetic edge features in [0, 1)
@@ -125,9 +142,10 @@ def main(argv=None):
         t0 = time.perf_counter()
         opt.zero_grad(set_to_none=True)
         # mean over ALL nodes: each rank sums its own rows' losses, divided by V
-        out = model(graph, feats) if R == 1 or dist is not None else model(graph, feats, values)
-        loss = F.cross_entropy(out, labels, reduction="sum") / V
-        loss.backward()
+        with torch.autocast("cuda", dtype=amp_dtype, enabled=amp_dtype is not None):
+            out = model(graph, feats) if R == 1 or dist is not None else model(graph, feats, values)
+            loss = F.cross_entropy(out.float(), labels, reduction="sum") / V
+        scaler.scale(loss).backward()
         if dist is not None:   # replicated weights: sum the ranks' gradients
             grads = [q.grad for q in model.parameters() if q.grad is not None]
             flat = torch.cat([g.reshape(-1) for g in grads])
@@ -138,7 +156,8 @@ def main(argv=None):
                 off += g.numel()
             loss = loss.detach().clone()
             dist.all_reduce(loss)
-        opt.step()
+        scaler.step(opt)   # plain opt.step() unless --amp fp16
+        scaler.update()
         torch.cuda.synchronize()
         times.append(time.perf_counter() - t0)
         losses.append(float(loss))
@@ -147,7 +166,7 @@ def main(argv=None):
     steady = times[2:] or times
     if rank == 0:
         print(f"{args.graph}: V={V} E={indices.numel()} layers={args.layers} hidden={args.hidden} "
-              f"k={args.maxk} relations={R} gpus={world}: "
+              f"k={args.maxk} relations={R} gpus={world} amp={args.amp}: "
               f"{sum(steady) / len(steady) * 1e3:.1f} ms/step, "
               f"loss {losses[0]:.3f} -> {losses[-1]:.3f}")
     if dist is not None:

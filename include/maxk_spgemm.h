@@ -26,6 +26,8 @@
  *             columns < dim_origin per row; the selector is a uint8, so
  *             dim_origin <= 256, as in the reference, spmm_maxk.cu:17)
  *      dense  out / grad fp32[num_rows,dim_origin];  dxs fp32[num_cols,k]
+ *    The *_t entry points near the end of this header take cbsr_data, out,
+ *    grad and dxs as fp16 or bf16 arrays of the same shapes.
  */
 #ifndef MAXK_SPGEMM_H
 #define MAXK_SPGEMM_H
@@ -507,6 +509,67 @@ int maxk_cbsr_scatter(const float *vals, const uint8_t *cbsr_sel, int num_rows, 
                       float *out, void *stream);
 int maxk_cbsr_mask(const float *src, const uint8_t *cbsr_sel, int num_rows, int k, int dim,
                    float *out, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Half-precision features (fp16 / bf16 in HBM, fp32 arithmetic).  The entry
+ * points below are the fp32 ones above with a storage type per feature
+ * array; with MAXK_F32 everywhere they run the fp32 kernels unchanged.  No
+ * reference counterpart (the reference is fp32 throughout).
+ *  - Edge values, partial rows (`parts`), carry / owner rows and the
+ *    backward's staging rows stay fp32: every product and every sum is fp32.
+ *  - Each output element is converted to its storage type once, by its only
+ *    writer, round-to-nearest-even; no kernel reads back a 2-byte output.
+ *    So |result - exact| <= u * |exact'| + the fp32 path's own error, with
+ *    exact' the fp32 result and u = 2^-11 (fp16) / 2^-8 (bf16).
+ *  - Every feature pointer (x, cbsr_data, dense_out, vals, src, out, grad,
+ *    dxs, parts), cbsr_sel of the forward / backward and the workspace must be
+ *    16-byte aligned (the kernels move >= 4 bytes per lane); a misaligned
+ *    pointer or an unknown dtype returns MAXK_E_ARG before any launch.
+ *  - 2-byte types take the plain CBSR only (no packed records, edge selectors
+ *    or halo records); compile-time k in {8, 16, 32, 64}, any other k runs
+ *    the generic kernels.
+ * maxk_topk_cbsr_t: x, cbsr_data and dense_out in `dtype`, ld in elements.
+ *   Selects exactly as maxk_topk_cbsr does on the up-cast row (the up-cast is
+ *   exact and keeps the order); cbsr_data / dense_out hold the input's bits.
+ * maxk_cbsr_scatter_t / maxk_cbsr_mask_t: moves of 2- or 4-byte elements.
+ * maxk_spgemm_forward_t: maxk_spgemm_forward_sum_parts with cbsr_data in
+ *   data_dtype and out in out_dtype (independent).  flags: 0 or
+ *   MAXK_FWD_CACHED_GATHER; MAXK_FWD_ACCUMULATE is taken with fp32 data and
+ *   out and no parts only (a 2-byte out would be rounded, added to and rounded
+ *   again: MAXK_E_ARG).  The column-blocked forward with half features is blocks
+ *   0..nb-2 with out_dtype = MAXK_F32 into the fp32 partials, then the last
+ *   block with `parts` and out_dtype = the feature type.
+ * maxk_sspmm_backward_t: maxk_sspmm_backward with grad in grad_dtype and dxs
+ *   in dxs_dtype.  With a 2-byte type algo must be MAXK_BWD_STAGED (or AUTO
+ *   with the CSC inputs and a workspace, which resolves to it); any other
+ *   algorithm returns MAXK_E_ARG.  A destination split over several
+ *   segmented-sum panels is summed in fp32 from carry and owner rows and
+ *   stored once, so the workspace of a 2-byte dxs has one more row per panel:
+ *   maxk_backward_workspace_bytes_t.
+ * ------------------------------------------------------------------------- */
+#define MAXK_F32 0
+#define MAXK_F16 1
+#define MAXK_BF16 2
+int maxk_topk_cbsr_t(const void *x, int dtype, int num_rows, int dim, int64_t ld, int k, int order,
+                     void *cbsr_data, uint8_t *cbsr_sel, void *dense_out, void *stream);
+int maxk_cbsr_scatter_t(const void *vals, int dtype, const uint8_t *cbsr_sel, int num_rows, int k,
+                        int dim, void *out, void *stream);
+int maxk_cbsr_mask_t(const void *src, int dtype, const uint8_t *cbsr_sel, int num_rows, int k,
+                     int dim, void *out, void *stream);
+int maxk_spgemm_forward_t(const int32_t *sched, int64_t num_panels, const int32_t *indptr,
+                          const int32_t *indices, const float *values, const void *cbsr_data,
+                          int data_dtype, const uint8_t *cbsr_sel, int num_rows, int dim_origin,
+                          int dim_k, int flags, const float *parts, int num_parts, void *out,
+                          int out_dtype, void *workspace, size_t workspace_bytes, void *stream);
+size_t maxk_backward_workspace_bytes_t(int algo, int64_t num_edges, int dim_k,
+                                       int64_t csc_num_panels, int dxs_dtype);
+int maxk_sspmm_backward_t(int algo, const int32_t *sched, int64_t num_panels,
+                          const int32_t *indptr, const int32_t *indices, const float *values,
+                          const void *grad, int grad_dtype, const uint8_t *cbsr_sel, int num_rows,
+                          int num_cols, int64_t num_edges, int dim_origin, int dim_k, void *dxs,
+                          int dxs_dtype, const int32_t *csc_pos, const int32_t *csc_sched,
+                          int64_t csc_num_panels, const int32_t *csc_indptr, void *workspace,
+                          size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
  * Exact drop-ins for the reference's extern "C" launchers

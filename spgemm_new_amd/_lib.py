@@ -43,6 +43,10 @@ MAXK_TOPK_ORDER_VALUE = 1
 MAXK_TOPK_ORDER_LANE = 2
 MAXK_FWD_ACCUMULATE = 1
 MAXK_FWD_CACHED_GATHER = 2
+# feature storage types of the *_t entry points
+MAXK_F32 = 0
+MAXK_F16 = 1
+MAXK_BF16 = 2
 DEFAULT_PANEL_COST = 2048
 DEFAULT_ROW_COST = 16
 
@@ -121,6 +125,14 @@ SIGNATURES = {
     "maxk_topk_cbsr": (_I, [_P, _I, _I, _L, _I, _I, _P, _P, _P, _P]),
     "maxk_cbsr_scatter": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "maxk_cbsr_mask": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "maxk_topk_cbsr_t": (_I, [_P, _I, _I, _I, _L, _I, _I, _P, _P, _P, _P]),
+    "maxk_cbsr_scatter_t": (_I, [_P, _I, _P, _I, _I, _I, _P, _P]),
+    "maxk_cbsr_mask_t": (_I, [_P, _I, _P, _I, _I, _I, _P, _P]),
+    "maxk_spgemm_forward_t": (_I, [_P, _L, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I,
+                                   _P, _S, _P]),
+    "maxk_backward_workspace_bytes_t": (_S, [_I, _L, _I, _L, _I]),
+    "maxk_sspmm_backward_t": (_I, [_I, _P, _L, _P, _P, _P, _P, _I, _P, _I, _I, _L, _I, _I, _P, _I,
+                                   _P, _P, _L, _P, _P, _S, _P]),
     "maxk_spmm_forward_warp4": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "maxk_spmm_backward_warp4": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
 }
@@ -171,6 +183,11 @@ def check(rc: int, what: str) -> None:
         if rc < 0:
             raise MaxKError(f"{what}: {_ERRORS.get(rc, 'error')} ({rc})")
         raise MaxKError(f"{what}: HIP error {rc}")
+
+
+def dtype_code(dtype) -> int | None:
+    """MAXK_F32 / MAXK_F16 / MAXK_BF16 of a torch dtype (None: not a feature type)."""
+    return {torch.float32: MAXK_F32, torch.float16: MAXK_F16, torch.bfloat16: MAXK_BF16}.get(dtype)
 
 
 def stream_ptr(device=None) -> int:

@@ -55,7 +55,9 @@ torch::Tensor spmm_maxk_forward(torch::Tensor warp4_metadata, torch::Tensor indi
     TORCH_CHECK(warp4_metadata.dtype() == torch::kInt32, "warp4_metadata must be int32");
     TORCH_CHECK(indices.dtype() == torch::kInt32, "indices must be int32");
     TORCH_CHECK(values.dtype() == torch::kFloat32, "values must be float32");
-    TORCH_CHECK(input_data.dtype() == torch::kFloat32, "input_data must be float32");
+    TORCH_CHECK(input_data.dtype() == torch::kFloat32,
+                "input_data must be float32 (this module is fp32 only; half-precision features "
+                "run through spgemm_new_amd.MaxKGraph)");
     TORCH_CHECK(sparse_selector.dtype() == torch::kUInt8, "sparse_selector must be uint8");
     const int num_v = (int)input_data.size(0);
     auto output = torch::zeros({num_v, kFullDim}, input_data.options());
@@ -81,7 +83,9 @@ torch::Tensor spmm_maxk_backward(torch::Tensor warp4_metadata, torch::Tensor ind
     TORCH_CHECK(warp4_metadata.dtype() == torch::kInt32, "warp4_metadata must be int32");
     TORCH_CHECK(indices.dtype() == torch::kInt32, "indices must be int32");
     TORCH_CHECK(values.dtype() == torch::kFloat32, "values must be float32");
-    TORCH_CHECK(grad_output.dtype() == torch::kFloat32, "grad_output must be float32");
+    TORCH_CHECK(grad_output.dtype() == torch::kFloat32,
+                "grad_output must be float32 (this module is fp32 only; half-precision features "
+                "run through spgemm_new_amd.MaxKGraph)");
     TORCH_CHECK(sparse_selector.dtype() == torch::kUInt8, "sparse_selector must be uint8");
     const int num_v = (int)grad_output.size(0), feat_in = (int)grad_output.size(1);
     auto grad_input = torch::zeros({num_v, dim_sparse}, grad_output.options());

@@ -24,6 +24,13 @@
 //              a wave's LDS, in-edges sorted by source row, one launch per
 //              source band so the G window stays cache-resident; edge records
 //              read into SGPRs (k = 32, 64).
+//  * Half-precision features (the *_t entry points): CBSR data, outputs and
+//    gradients may be fp16 / bf16 arrays (storage-type template parameters TD /
+//    TG on the forward and the STAGED push; 4- or 8-byte loads per lane, raw
+//    words up-cast where they are consumed).  Products, sums, carry / owner
+//    rows and staging rows stay fp32; an output element is rounded once, by
+//    its only writer (flush_row_as, carry_fixup_owner_kernel<.., true>,
+//    bwd_segsum_owner_kernel / bwd_fixup_owner_kernel).  DESIGN.md 4b.
 //  * wave64 everywhere; no CUDA-isms, no warp32 tiling.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -31,10 +38,13 @@
 
 #include "../../include/maxk_spgemm.h"
 #include "tile_format.h"
+#include "maxk_types.h"
 
 #define MAXK_VERSION_STRING "maxk-mi355x 0.1 (gfx950, wave64)"
 
 namespace {
+
+using namespace maxk;
 
 constexpr int kWave = 64;
 constexpr int kWavesPerBlock = 4;
@@ -182,11 +192,14 @@ __global__ __launch_bounds__(256) void exclusive_scan_1block(int32_t *c, int n, 
 #ifndef FWD_VEC64
 #define FWD_VEC64 4   // ... at k = 64 (development knob)
 #endif
-template <int K>
+// ES: bytes per CBSR data element.  2-byte data takes at least two entries
+// (one dword) per lane, so k = 8 runs 4 lanes per edge and 16 row copies.
+template <int K, int ES = 4>
 struct FwdLayout {
-    static constexpr int VEC = K > 64 ? 4 : K == 64 ? FWD_VEC64
-                             : K >= 32 ? FWD_VEC32
-                             : (K >= 16 ? FWD_VEC16 : (K >= 8 ? FWD_VEC8 : 1));
+    static constexpr int VEC4 = K > 64 ? 4 : K == 64 ? FWD_VEC64
+                              : K >= 32 ? FWD_VEC32
+                              : (K >= 16 ? FWD_VEC16 : (K >= 8 ? FWD_VEC8 : 1));
+    static constexpr int VEC = ES == 2 && VEC4 < 2 ? 2 : VEC4;
     static constexpr int LPE = K / VEC;
     static constexpr int EPS = kWave / LPE;
 };
@@ -198,10 +211,10 @@ __host__ __device__ constexpr int fwd_copies_generic(int k)
     return k >= kWave ? 1 : (kWave / k < 8 ? kWave / k : 8);
 }
 
-template <int K>
+template <int K, int ES = 4>
 __host__ __device__ constexpr int fwd_copies(int k)
 {
-    if constexpr (K > 0) return FwdLayout<K>::EPS;
+    if constexpr (K > 0) return FwdLayout<K, ES>::EPS;
     else return fwd_copies_generic(k);
 }
 
@@ -210,6 +223,45 @@ struct VecT;
 template <> struct VecT<4> { typedef f4 D; typedef uint32_t S; };
 template <> struct VecT<2> { typedef float D __attribute__((ext_vector_type(2))); typedef uint16_t S; };
 template <> struct VecT<1> { typedef float D; typedef uint8_t S; };
+
+// What a lane's gather of VEC consecutive CBSR entries of storage type TD
+// returns: the fp32 vector itself, or the raw 4 / 8 bytes of 2-byte entries.
+// The raw words are up-cast (up_cast) only where they are consumed: converting
+// at the load would make every gather wait for its data before the next one is
+// issued (s_waitcnt vmcnt after each load instead of U gathers in flight).
+template <typename TD, int VEC>
+struct RawVec { typedef typename VecT<VEC>::D T; };
+template <> struct RawVec<f16_t, 2> { typedef uint32_t T; };
+template <> struct RawVec<bf16_t, 2> { typedef uint32_t T; };
+template <> struct RawVec<f16_t, 4> { typedef u32x2 T; };
+template <> struct RawVec<bf16_t, 4> { typedef u32x2 T; };
+
+template <typename TD, int VEC, bool NTD>
+__device__ __forceinline__ typename RawVec<TD, VEC>::T load_half_raw(const TD *p)
+{
+    static_assert(sizeof(TD) == 2 && (VEC == 2 || VEC == 4), "a lane loads at least one dword");
+    using R = typename RawVec<TD, VEC>::T;
+    if constexpr (NTD) return __builtin_nontemporal_load(reinterpret_cast<const R *>(p));
+    else return *reinterpret_cast<const R *>(p);
+}
+
+template <typename TD, int VEC>
+__device__ __forceinline__ typename VecT<VEC>::D up_cast(typename RawVec<TD, VEC>::T w)
+{
+    if constexpr (sizeof(TD) == 4) {
+        return w;
+    } else {
+        constexpr int DT = DType<TD>::id;
+        typename VecT<VEC>::D d;
+        if constexpr (VEC == 2) {
+            d.x = word_lo<DT>(w); d.y = word_hi<DT>(w);
+        } else {
+            d.x = word_lo<DT>(w.x); d.y = word_hi<DT>(w.x);
+            d.z = word_lo<DT>(w.y); d.w = word_hi<DT>(w.y);
+        }
+        return d;
+    }
+}
 
 template <int VEC>
 __device__ __forceinline__ void rmw_acc(float *acc, typename VecT<VEC>::S sb, float v,
@@ -286,15 +338,18 @@ __device__ __forceinline__ void fwd_pf_load(FwdPf &pf, int b, int pend,
     }
 }
 
-template <int K, int RS = 0, bool ESEL = false, bool NTD = true, bool PF = false>
+// TD: storage type of the CBSR data (float; f16_t / bf16_t on the plain path only).
+template <int K, int RS = 0, bool ESEL = false, bool NTD = true, bool PF = false,
+          typename TD = float>
 __device__ __forceinline__ void fwd_edges_vec(int e0, int e1, const int32_t *__restrict__ idx,
                                               const float *__restrict__ val,
-                                              const float *__restrict__ data,
+                                              const TD *__restrict__ data,
                                               const uint8_t *__restrict__ sel, float *acc,
                                               uint8_t *__restrict__ esel, FwdPf *pf = nullptr,
                                               int pend = 0)
 {
-    using Lay = FwdLayout<K>;
+    static_assert(sizeof(TD) == 4 || (RS == 0 && !ESEL), "2-byte data: plain CBSR only");
+    using Lay = FwdLayout<K, (int)sizeof(TD)>;
     constexpr int VEC = Lay::VEC, LPE = Lay::LPE, EPS = Lay::EPS;
     constexpr int STEPS = kWave / EPS;  // steps per 64-edge batch
 #ifndef FWD_U
@@ -322,7 +377,7 @@ __device__ __forceinline__ void fwd_edges_vec(int e0, int e1, const int32_t *__r
 #pragma unroll
         for (int s0 = 0; s0 < STEPS; s0 += U) {
             if (s0 * EPS >= n) break;
-            D d[U];
+            typename RawVec<TD, VEC>::T d[U];  // fp32: D itself
             SB sb[U];
             float v[U];
 #pragma unroll
@@ -337,7 +392,9 @@ __device__ __forceinline__ void fwd_edges_vec(int e0, int e1, const int32_t *__r
                         // selector words plain (nt 4-B loads measured slower)
                         // (NTD false: cacheable, for the column-blocked forward whose
                         // block-major sweep re-reads a block's rows from L2)
-                        if constexpr (NTD)
+                        if constexpr (sizeof(TD) == 2)
+                            d[u] = load_half_raw<TD, VEC, NTD>(data + off);
+                        else if constexpr (NTD)
                             d[u] = __builtin_nontemporal_load(reinterpret_cast<const D *>(data + off));
                         else
                             d[u] = *reinterpret_cast<const D *>(data + off);
@@ -357,7 +414,7 @@ __device__ __forceinline__ void fwd_edges_vec(int e0, int e1, const int32_t *__r
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int t = (s0 + u) * EPS + slot;
-                if (t < n) rmw_acc<VEC>(my_acc, sb[u], v[u], d[u]);
+                if (t < n) rmw_acc<VEC>(my_acc, sb[u], v[u], up_cast<TD, VEC>(d[u]));
                 if constexpr (ESEL) {
                     // one dword store per 4 selector bytes: neighbouring lanes of the
                     // edge hand theirs over (byte / short stores ran at ~1 TB/s)
@@ -392,10 +449,11 @@ __device__ __forceinline__ void fwd_edges_vec(int e0, int e1, const int32_t *__r
 
 
 // Any k: one CBSR entry per lane, EPS = 64 / min(k, 64) row copies.
+template <typename TD = float>
 __device__ __forceinline__ void fwd_edges_scalar(int e0, int e1, int k,
                                                  const int32_t *__restrict__ idx,
                                                  const float *__restrict__ val,
-                                                 const float *__restrict__ data,
+                                                 const TD *__restrict__ data,
                                                  const uint8_t *__restrict__ sel, float *acc,
                                                  uint8_t *__restrict__ esel)
 {
@@ -410,7 +468,7 @@ __device__ __forceinline__ void fwd_edges_scalar(int e0, int e1, int k,
                 const int c = idx[my];
                 const float v = val[my];
                 const size_t off = (size_t)c * k + l;
-                my_acc[sel[off]] += v * data[off];
+                my_acc[sel[off]] += v * load_f32(data + off);
                 if (esel) esel[(size_t)my * k + l] = sel[off];
             }
         }
@@ -420,22 +478,22 @@ __device__ __forceinline__ void fwd_edges_scalar(int e0, int e1, int k,
             const float v = val[e];
             for (int l = lane; l < k; l += kWave) {
                 const size_t off = (size_t)c * k + l;
-                acc[sel[off]] += v * data[off];
+                acc[sel[off]] += v * load_f32(data + off);
                 if (esel) esel[(size_t)e * k + l] = sel[off];
             }
         }
     }
 }
 
-template <int K, int RS = 0, bool ESEL = false, bool NTD = true>
+template <int K, int RS = 0, bool ESEL = false, bool NTD = true, typename TD = float>
 __device__ __forceinline__ void fwd_edges(int e0, int e1, int k, const int32_t *__restrict__ idx,
                                           const float *__restrict__ val,
-                                          const float *__restrict__ data,
+                                          const TD *__restrict__ data,
                                           const uint8_t *__restrict__ sel, float *acc,
                                           uint8_t *__restrict__ esel = nullptr)
 {
     if constexpr (K > 0)
-        fwd_edges_vec<K, RS, ESEL, NTD>(e0, e1, idx, val, data, sel, acc, esel);
+        fwd_edges_vec<K, RS, ESEL, NTD, false, TD>(e0, e1, idx, val, data, sel, acc, esel);
     else
         fwd_edges_scalar(e0, e1, k, idx, val, data, sel, acc, ESEL ? esel : nullptr);
 }
@@ -504,6 +562,69 @@ __device__ __forceinline__ void flush_row(float *acc, int copies, float *__restr
     wave_sync_lds();
 }
 
+// Four / one fp32 sums stored as elements of the run-time storage type odt
+// (wave-uniform): the single rounding of an output element, by its only writer.
+__device__ __forceinline__ void store4_as(void *row, int c4, f4 a, int odt)
+{
+    if (odt == MAXK_F32) {
+        __builtin_nontemporal_store(a, static_cast<f4 *>(row) + c4);
+    } else {
+        u32x2 w;
+        w.x = f32_to_half_bits(a.x, odt) | (f32_to_half_bits(a.y, odt) << 16);
+        w.y = f32_to_half_bits(a.z, odt) | (f32_to_half_bits(a.w, odt) << 16);
+        __builtin_nontemporal_store(w, static_cast<u32x2 *>(row) + c4);
+    }
+}
+__device__ __forceinline__ void store1_as(void *row, int c, float a, int odt)
+{
+    if (odt == MAXK_F32) static_cast<float *>(row)[c] = a;
+    else static_cast<uint16_t *>(row)[c] = (uint16_t)f32_to_half_bits(a, odt);
+}
+
+// flush_row<kStore> for an output row of storage type odt (the *_t entry
+// points): the same sums in the same order, converted once at the store.
+__device__ __forceinline__ void flush_row_as(float *acc, int copies, void *__restrict__ dst, int odt,
+                                             int dim, const float *__restrict__ sp, int nsp,
+                                             size_t ss)
+{
+    const int lane = lane_id();
+    wave_sync_lds();
+    if ((dim & 3) == 0) {
+        for (int c4 = lane; c4 < (dim >> 2); c4 += kWave) {
+            f4 a = reinterpret_cast<f4 *>(acc)[c4];
+            reinterpret_cast<f4 *>(acc)[c4] = f4{0.f, 0.f, 0.f, 0.f};
+            for (int cp = 1; cp < copies; ++cp) {
+                f4 *q = reinterpret_cast<f4 *>(acc + cp * kMaxDim) + c4;
+                a += *q;
+                *q = f4{0.f, 0.f, 0.f, 0.f};
+            }
+            if (sp) {
+                f4 s = __builtin_nontemporal_load(reinterpret_cast<const f4 *>(sp) + c4);
+                for (int q = 1; q < nsp; ++q)
+                    s += __builtin_nontemporal_load(reinterpret_cast<const f4 *>(sp + q * ss) + c4);
+                a = s + a;
+            }
+            store4_as(dst, c4, a, odt);
+        }
+    } else {
+        for (int c = lane; c < dim; c += kWave) {
+            float a = acc[c];
+            acc[c] = 0.f;
+            for (int cp = 1; cp < copies; ++cp) {
+                a += acc[cp * kMaxDim + c];
+                acc[cp * kMaxDim + c] = 0.f;
+            }
+            if (sp) {
+                float t = sp[c];
+                for (int q = 1; q < nsp; ++q) t += sp[q * ss + c];
+                a = t + a;
+            }
+            store1_as(dst, c, a, odt);
+        }
+    }
+    wave_sync_lds();
+}
+
 __device__ __forceinline__ void zero_lds(float *acc, int n)
 {
     for (int c = lane_id(); c < n; c += kWave) acc[c] = 0.f;
@@ -521,19 +642,25 @@ constexpr int fwd_waves_per_eu()
 {
     return K == 16 && RS > 0 && !ESEL ? 5 : 1;
 }
-template <int K, int RS = 0, bool ACC = false, bool ESEL = false, bool NTD = true>
+// TD: storage type of the CBSR data.  RTO (the *_t entry points): out is an
+// array of the run-time storage type odt; the owned rows are converted at their
+// store (flush_row_as), carry and owner rows stay fp32.
+template <int K, int RS = 0, bool ACC = false, bool ESEL = false, bool NTD = true,
+          typename TD = float, bool RTO = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(fwd_waves_per_eu<K, RS, ESEL>())))
 void fwd_panel_kernel(
     const int2 *__restrict__ sched, int64_t num_panels, const int32_t *__restrict__ indptr,
     const int32_t *__restrict__ idx, const float *__restrict__ val,
-    const float *__restrict__ data, const uint8_t *__restrict__ sel, int num_rows, int dim,
+    const TD *__restrict__ data, const uint8_t *__restrict__ sel, int num_rows, int dim,
     int k, float *__restrict__ out, float *__restrict__ carry, int32_t *__restrict__ carry_row,
     float *__restrict__ owner, uint8_t *__restrict__ esel, const float *__restrict__ sump,
-    int nsump)
+    int nsump, int odt)
 {
+    static_assert(!RTO || !ACC, "a typed output row is written once, never added to");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int dimp = (dim + 3) & ~3;
-    const int copies = fwd_copies<K>(k);
+    const int copies = fwd_copies<K, (int)sizeof(TD)>(k);
+    [[maybe_unused]] const size_t orow = (size_t)dim * dtype_bytes(odt);  // RTO: bytes per output row
     // selectors are uint8, so a full 256-float row per copy is never overrun
     float *acc = lds + (threadIdx.x / kWave) * copies * kMaxDim;
     const int64_t w = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
@@ -554,9 +681,12 @@ void fwd_panel_kernel(
         for (int r = i0; r < i1; ++r) {
             const int re = indptr[r + 1];
             if (e < re)
-                fwd_edges_vec<K, RS, ESEL, NTD, true>(e, re, idx, val, data, sel, acc, esel, &pf, j1);
+                fwd_edges_vec<K, RS, ESEL, NTD, true, TD>(e, re, idx, val, data, sel, acc, esel, &pf, j1);
             if (r == i0 && split_first)
                 flush_row<kStore>(acc, copies, owner + (size_t)w * dimp, dim);
+            else if constexpr (RTO)
+                flush_row_as(acc, copies, reinterpret_cast<char *>(out) + r * orow, odt, dim,
+                             sump ? sump + (size_t)r * dim : nullptr, nsump, (size_t)num_rows * dim);
             else if (!ACC && sump)
                 flush_row<kStore>(acc, copies, out + (size_t)r * dim, dim, sump + (size_t)r * dim,
                                   nsump, (size_t)num_rows * dim);
@@ -568,16 +698,19 @@ void fwd_panel_kernel(
             const int eb = e > indptr[i1] ? e : indptr[i1];
             if (eb < j1) {
                 if (eb != e) fwd_pf_load(pf, eb, j1, idx, val);
-                fwd_edges_vec<K, RS, ESEL, NTD, true>(eb, j1, idx, val, data, sel, acc, esel, &pf, j1);
+                fwd_edges_vec<K, RS, ESEL, NTD, true, TD>(eb, j1, idx, val, data, sel, acc, esel, &pf, j1);
                 has_carry = 1;
             }
         }
     } else {
         for (int r = i0; r < i1; ++r) {
             const int re = indptr[r + 1];
-            if (e < re) fwd_edges<K, RS, ESEL, NTD>(e, re, k, idx, val, data, sel, acc, esel);
+            if (e < re) fwd_edges<K, RS, ESEL, NTD, TD>(e, re, k, idx, val, data, sel, acc, esel);
             if (r == i0 && split_first)
                 flush_row<kStore>(acc, copies, owner + (size_t)w * dimp, dim);
+            else if constexpr (RTO)
+                flush_row_as(acc, copies, reinterpret_cast<char *>(out) + r * orow, odt, dim,
+                             sump ? sump + (size_t)r * dim : nullptr, nsump, (size_t)num_rows * dim);
             else if (!ACC && sump)
                 flush_row<kStore>(acc, copies, out + (size_t)r * dim, dim, sump + (size_t)r * dim,
                                   nsump, (size_t)num_rows * dim);
@@ -588,7 +721,7 @@ void fwd_panel_kernel(
         if (i1 < num_rows) {
             const int eb = e > indptr[i1] ? e : indptr[i1];
             if (eb < j1) {
-                fwd_edges<K, RS, ESEL, NTD>(eb, j1, k, idx, val, data, sel, acc, esel);
+                fwd_edges<K, RS, ESEL, NTD, TD>(eb, j1, k, idx, val, data, sel, acc, esel);
                 has_carry = 1;
             }
         }
@@ -667,13 +800,16 @@ __global__ __launch_bounds__(kBlock) void carry_fixup_kernel(
 // owner (the first panel whose end lies past row r) there can be empty panels
 // (panel_cost < row_cost: boundaries inside a row's end cost), which carry
 // nothing and have no owner slot.
-template <bool ACC>
+// RTO: out has the run-time storage type odt; the fp32 sum is converted at its
+// one store (the row's only writer).
+template <bool ACC, bool RTO = false>
 __global__ __launch_bounds__(kBlock) void carry_fixup_owner_kernel(
     const int2 *__restrict__ sched, int64_t num_panels, const float *__restrict__ carry,
     const float *__restrict__ owner, const int32_t *__restrict__ carry_row,
     float *__restrict__ out, int dim, int dimp, int num_rows, const float *__restrict__ sump,
-    int nsump)
+    int nsump, int odt)
 {
+    static_assert(!RTO || !ACC, "a typed output row is written once, never added to");
     const int64_t w = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
     if (w >= num_panels) return;
     const int r = carry_row[w];
@@ -683,6 +819,7 @@ __global__ __launch_bounds__(kBlock) void carry_fixup_owner_kernel(
     int64_t own = w_end;
     while (sched[own + 1].x <= r) ++own;   // the panel that owns row r (exists: r < num_rows)
     float *dst = out + (size_t)r * dim;
+    [[maybe_unused]] void *dst_as = reinterpret_cast<char *>(out) + (size_t)r * dim * dtype_bytes(odt);  // RTO
     if ((dim & 3) == 0) {
         for (int c4 = lane_id(); c4 < (dim >> 2); c4 += kWave) {
             f4 a = reinterpret_cast<const f4 *>(owner + (size_t)own * dimp)[c4];
@@ -694,7 +831,8 @@ __global__ __launch_bounds__(kBlock) void carry_fixup_owner_kernel(
                 for (int q = 1; q < nsump; ++q) t += sp[(size_t)q * num_rows * (dim >> 2)];
                 a = t + a;
             }
-            __builtin_nontemporal_store(a, reinterpret_cast<f4 *>(dst) + c4);
+            if constexpr (RTO) store4_as(dst_as, c4, a, odt);
+            else __builtin_nontemporal_store(a, reinterpret_cast<f4 *>(dst) + c4);
         }
     } else {
         for (int c = lane_id(); c < dim; c += kWave) {
@@ -705,7 +843,8 @@ __global__ __launch_bounds__(kBlock) void carry_fixup_owner_kernel(
                 for (int q = 1; q < nsump; ++q) t += sump[((size_t)q * num_rows + r) * dim + c];
                 a = t + a;
             }
-            dst[c] = ACC ? dst[c] + a : a;
+            if constexpr (RTO) store1_as(dst_as, c, a, odt);
+            else dst[c] = ACC ? dst[c] + a : a;
         }
     }
 }
@@ -1206,16 +1345,31 @@ __global__ __launch_bounds__(kBlock) void fwd_warp4_kernel(
 // ---------------------------------------------------------------------------
 // Backward
 // ---------------------------------------------------------------------------
-// Stage G[r, 0:dim] into the wave's LDS row.
-__device__ __forceinline__ void stage_row(float *gs, const float *__restrict__ g, int dim)
+// Four consecutive gradient entries of a lane: a 16-byte load of fp32, or the
+// raw 8 bytes of a 2-byte storage type TG, up-cast (exact) by g4_f32 where the
+// row is written to LDS -- not at the load, which may be a prefetch.
+template <typename TG> struct RawG4 { typedef typename RawVec<TG, 4>::T T; };
+template <bool NT, typename TG>
+__device__ __forceinline__ typename RawG4<TG>::T load_g4(const TG *p)
+{
+    using R = typename RawG4<TG>::T;
+    if constexpr (NT) return __builtin_nontemporal_load(reinterpret_cast<const R *>(p));
+    else return *reinterpret_cast<const R *>(p);
+}
+template <typename TG>
+__device__ __forceinline__ f4 g4_f32(typename RawG4<TG>::T w) { return up_cast<TG, 4>(w); }
+
+// Stage G[r, 0:dim] into the wave's LDS row (fp32 there whatever G's storage type).
+template <typename TG = float>
+__device__ __forceinline__ void stage_row(float *gs, const TG *__restrict__ g, int dim)
 {
     wave_sync_lds();
     const int lane = lane_id();
     if ((dim & 3) == 0) {
         for (int c4 = lane; c4 < (dim >> 2); c4 += kWave)
-            reinterpret_cast<f4 *>(gs)[c4] = reinterpret_cast<const f4 *>(g)[c4];
+            reinterpret_cast<f4 *>(gs)[c4] = g4_f32<TG>(load_g4<false>(g + 4 * c4));
     } else {
-        for (int c = lane; c < dim; c += kWave) gs[c] = g[c];
+        for (int c = lane; c < dim; c += kWave) gs[c] = load_f32(g + c);
     }
     // selector bytes >= dim (invalid input) read 0: every algorithm then gives
     // such an entry no contribution, as LOCAL and the forward do
@@ -1504,11 +1658,13 @@ __device__ __forceinline__ void bwd_edges_stage_scalar(int e0, int e1, int k,
 }
 
 // Panel-scheduled backward push (ATOMIC when P == nullptr, STAGED otherwise).
-template <int K, bool STAGED, bool ESEL = false, int PM = kPmCsc>
+// TG: storage type of the gradient rows; they are staged in LDS as fp32, so the
+// products and the staging rows P are fp32 for every TG.
+template <int K, bool STAGED, bool ESEL = false, int PM = kPmCsc, typename TG = float>
 __global__ __launch_bounds__(kBlock) void bwd_panel_kernel(
     const int2 *__restrict__ sched, int64_t num_panels, const int32_t *__restrict__ indptr,
     const int32_t *__restrict__ idx, const float *__restrict__ val,
-    const float *__restrict__ grad, const uint8_t *__restrict__ sel,
+    const TG *__restrict__ grad, const uint8_t *__restrict__ sel,
     const int32_t *__restrict__ csc_pos, int num_rows, int dim, int k,
     float *__restrict__ dxs, float *__restrict__ P)
 {
@@ -1526,7 +1682,7 @@ __global__ __launch_bounds__(kBlock) void bwd_panel_kernel(
             // selector gathers run: one f4 of G per lane, one BwdPf per lane
             constexpr bool CSRP = PM == kPmEdge || PM == kPmAppend;
             const int lane = lane_id();
-            f4 gn = f4{0.f, 0.f, 0.f, 0.f};
+            typename RawG4<TG>::T gn = {};
             int gn_row = -1;
             BwdPf pf;
             bool first = true;
@@ -1536,16 +1692,16 @@ __global__ __launch_bounds__(kBlock) void bwd_panel_kernel(
                 const int ee = re < j1 ? re : j1;
                 if (eb >= ee) continue;
                 if (gn_row != r)
-                    gn = __builtin_nontemporal_load(reinterpret_cast<const f4 *>(grad + (size_t)r * dim) + lane);
+                    gn = load_g4<true>(grad + (size_t)r * dim + 4 * lane);
                 if (first) {
                     bwd_pf_load<CSRP>(pf, eb, j1, idx, val, csc_pos);
                     first = false;
                 }
                 wave_sync_lds();
-                reinterpret_cast<f4 *>(gs)[lane] = gn;
+                reinterpret_cast<f4 *>(gs)[lane] = g4_f32<TG>(gn);
                 wave_sync_lds();
                 if (r < rlast) {
-                    gn = __builtin_nontemporal_load(reinterpret_cast<const f4 *>(grad + (size_t)(r + 1) * dim) + lane);
+                    gn = load_g4<true>(grad + (size_t)(r + 1) * dim + 4 * lane);
                     gn_row = r + 1;
                 }
                 bwd_edges_stage_vec<K, ESEL, PM, true>(eb, ee, idx, val, csc_pos, sel, gs, P,
@@ -2024,6 +2180,105 @@ __global__ __launch_bounds__(kBlock) void bwd_segsum_kernel(
             }
         }
         if (lane == 0) carry_row[w] = has ? i1 : -1;
+    }
+}
+
+// STAGED phase 2 for a dXs of a 2-byte storage type (maxk_sspmm_backward_t).
+// bwd_segsum_kernel + carry_fixup_kernel store a split destination's row and
+// then read, add to and store it again, which in a 2-byte type would round
+// twice.  Here the forward's scheme: a destination that began in an earlier
+// panel leaves its part in this panel's fp32 owner slot, the earlier panels
+// theirs in their carry rows, and bwd_fixup_owner_kernel sums them in panel
+// order and stores the row -- one writer and one rounding per element.
+template <int K>
+__global__ __launch_bounds__(kBlock) void bwd_segsum_owner_kernel(
+    const int2 *__restrict__ sched, int64_t num_panels, const int32_t *__restrict__ cptr,
+    const float *__restrict__ P, int num_rows, int k, void *__restrict__ dxs, int odt,
+    float *__restrict__ carry, int32_t *__restrict__ carry_row, float *__restrict__ owner)
+{
+    const int64_t w = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
+    if (w >= num_panels) return;
+    const int lane = lane_id();
+    const int2 a = sched[w], b = sched[w + 1];
+    const int i0 = a.x, j0 = a.y, i1 = b.x, j1 = b.y;
+    const bool split_first = i0 < i1 && j0 > cptr[i0];
+    const size_t drow = (size_t)k * dtype_bytes(odt);
+    int e = j0;
+    if constexpr (K > 0) {
+        constexpr int LPE = K / 4;
+        const int sub = lane % LPE;
+        const bool writer = lane < LPE;
+        for (int c = i0; c < i1; ++c) {
+            const int ce = cptr[c + 1];
+            const f4 s = seg_sum_vec<K>(e, ce, P);
+            if (writer) {
+                if (c == i0 && split_first) reinterpret_cast<f4 *>(owner + (size_t)w * K)[sub] = s;
+                else store4_as(static_cast<char *>(dxs) + c * drow, sub, s, odt);
+            }
+            e = ce;
+        }
+        int has = 0;
+        f4 s = f4{0.f, 0.f, 0.f, 0.f};
+        if (i1 < num_rows) {
+            const int eb = e > cptr[i1] ? e : cptr[i1];
+            if (eb < j1) {
+                s = seg_sum_vec<K>(eb, j1, P);
+                has = 1;
+            }
+        }
+        if (has && writer) reinterpret_cast<f4 *>(carry + (size_t)w * K)[sub] = s;
+        if (lane == 0) carry_row[w] = has ? i1 : -1;
+    } else {
+        // generic k: lane l accumulates column l (and l+64, ...)
+        for (int c = i0; c < i1; ++c) {
+            const int ce = cptr[c + 1];
+            for (int l = lane; l < k; l += kWave) {
+                float s = 0.f;
+                for (int q = e; q < ce; ++q) s += P[(size_t)q * k + l];
+                if (c == i0 && split_first) owner[(size_t)w * k + l] = s;
+                else store1_as(static_cast<char *>(dxs) + c * drow, l, s, odt);
+            }
+            e = ce;
+        }
+        int has = 0;
+        if (i1 < num_rows) {
+            const int eb = e > cptr[i1] ? e : cptr[i1];
+            if (eb < j1) {
+                for (int l = lane; l < k; l += kWave) {
+                    float s = 0.f;
+                    for (int q = eb; q < j1; ++q) s += P[(size_t)q * k + l];
+                    carry[(size_t)w * k + l] = s;
+                }
+                has = 1;
+            }
+        }
+        if (lane == 0) carry_row[w] = has ? i1 : -1;
+    }
+}
+
+// Destination r split over segmented-sum panels w .. w_end (carries of w ..
+// w_end-1, the owner's part in owner slot `own`): summed in fp32 in panel
+// order by the wave of its first panel and stored once (carry_fixup_owner_kernel's
+// walk; empty panels between the last carrier and the owner have no slot).
+__global__ __launch_bounds__(kBlock) void bwd_fixup_owner_kernel(
+    const int2 *__restrict__ sched, int64_t num_panels, const float *__restrict__ carry,
+    const float *__restrict__ owner, const int32_t *__restrict__ carry_row, void *__restrict__ dxs,
+    int odt, int k)
+{
+    const int64_t w = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
+    if (w >= num_panels) return;
+    const int r = carry_row[w];
+    if (r < 0 || (w > 0 && carry_row[w - 1] == r)) return;
+    int64_t w_end = w + 1;
+    while (w_end < num_panels && carry_row[w_end] == r) ++w_end;
+    int64_t own = w_end;
+    while (sched[own + 1].x <= r) ++own;   // the panel that owns destination r
+    void *dst = static_cast<char *>(dxs) + (size_t)r * k * dtype_bytes(odt);
+    for (int c = lane_id(); c < k; c += kWave) {
+        float a = carry[(size_t)w * k + c];
+        for (int64_t v = w + 1; v < w_end; ++v) a += carry[(size_t)v * k + c];
+        a += owner[(size_t)own * k + c];
+        store1_as(dst, c, a, odt);
     }
 }
 
@@ -3696,6 +3951,11 @@ __global__ __launch_bounds__(kBlock) void zero_kernel(float *__restrict__ p, siz
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) p[i] = 0.f;
 }
 
+__global__ void zero_u16_kernel(uint16_t *__restrict__ p, size_t n)
+{
+    for (size_t i = threadIdx.x; i < n; i += blockDim.x) p[i] = 0;
+}
+
 // ---------------------------------------------------------------------------
 // Host-side dispatch
 // ---------------------------------------------------------------------------
@@ -3739,8 +3999,8 @@ int dispatch_k(int k, Args &&...args)
 
 size_t row_lds_bytes() { return (size_t)kWavesPerBlock * kMaxDim * sizeof(float); }
 
-template <int K>
-size_t fwd_lds_bytes(int k) { return (size_t)kWavesPerBlock * fwd_copies<K>(k) * kMaxDim * sizeof(float); }
+template <int K, int ES = 4>
+size_t fwd_lds_bytes(int k) { return (size_t)kWavesPerBlock * fwd_copies<K, ES>(k) * kMaxDim * sizeof(float); }
 
 inline int fwd_fixup(const int32_t *sched, int64_t P, const float *carry, const float *owner,
                      const int32_t *carry_row, float *out, int dim, bool acc, hipStream_t st,
@@ -3752,10 +4012,11 @@ inline int fwd_fixup(const int32_t *sched, int64_t P, const float *carry, const 
     if (acc)
         hipLaunchKernelGGL(carry_fixup_owner_kernel<true>, dim3((unsigned)blocks), dim3(kBlock), 0,
                            st, sc, P, carry, owner, carry_row, out, dim, dimp, num_rows,
-                           (const float *)nullptr, 0);
+                           (const float *)nullptr, 0, MAXK_F32);
     else
         hipLaunchKernelGGL(carry_fixup_owner_kernel<false>, dim3((unsigned)blocks), dim3(kBlock), 0,
-                           st, sc, P, carry, owner, carry_row, out, dim, dimp, num_rows, sump, nsump);
+                           st, sc, P, carry, owner, carry_row, out, dim, dimp, num_rows, sump, nsump,
+                           MAXK_F32);
     return launch_status();
 }
 
@@ -3774,12 +4035,48 @@ struct FwdPanel {
                     : acc ? fwd_panel_kernel<K, 0, true> : fwd_panel_kernel<K, 0, false>;
         hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kBlock), fwd_lds_bytes<K>(k), st,
                            reinterpret_cast<const int2 *>(sched), P, indptr, idx, val, data, sel,
-                           V, dim, k, out, carry, carry_row, owner, esel, sump, nsump);
+                           V, dim, k, out, carry, carry_row, owner, esel, sump, nsump, MAXK_F32);
         int rc = launch_status();
         if (rc) return rc;
         return fwd_fixup(sched, P, carry, owner, carry_row, out, dim, acc, st, V, sump, nsump);
     }
 };
+
+// Forward of maxk_spgemm_forward_t: CBSR data of storage type TD, out of the
+// run-time type odt.  Compile-time k in {8, 16, 32, 64}, any other k generic.
+template <int K, typename TD>
+int fwd_panel_typed(const int32_t *sched, int64_t P, const int32_t *indptr, const int32_t *idx,
+                    const float *val, const void *data, const uint8_t *sel, int V, int dim, int k,
+                    void *out, int odt, float *carry, int32_t *carry_row, float *owner,
+                    hipStream_t st, bool cached, const float *sump, int nsump)
+{
+    const int64_t blocks = ceil_div(P, kWavesPerBlock);
+    auto kern = cached ? fwd_panel_kernel<K, 0, false, false, false, TD, true>
+                       : fwd_panel_kernel<K, 0, false, false, true, TD, true>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kBlock),
+                       (fwd_lds_bytes<K, (int)sizeof(TD)>(k)), st,
+                       reinterpret_cast<const int2 *>(sched), P, indptr, idx, val,
+                       static_cast<const TD *>(data), sel, V, dim, k, static_cast<float *>(out),
+                       carry, carry_row, owner, (uint8_t *)nullptr, sump, nsump, odt);
+    int rc = launch_status();
+    if (rc) return rc;
+    hipLaunchKernelGGL((carry_fixup_owner_kernel<false, true>), dim3((unsigned)blocks), dim3(kBlock),
+                       0, st, reinterpret_cast<const int2 *>(sched), P, carry, owner, carry_row,
+                       static_cast<float *>(out), dim, (dim + 3) & ~3, V, sump, nsump, odt);
+    return launch_status();
+}
+
+template <typename TD, typename... Args>
+int fwd_typed_k(int k, Args &&...args)
+{
+    switch (k) {
+    case 8: return fwd_panel_typed<8, TD>(args...);
+    case 16: return fwd_panel_typed<16, TD>(args...);
+    case 32: return fwd_panel_typed<32, TD>(args...);
+    case 64: return fwd_panel_typed<64, TD>(args...);
+    default: return fwd_panel_typed<0, TD>(args...);
+    }
+}
 
 template <int K>
 struct FwdPanelPacked {
@@ -3798,7 +4095,7 @@ struct FwdPanelPacked {
                                fwd_lds_bytes<K>(k), st, reinterpret_cast<const int2 *>(sched), P,
                                indptr, idx, val, reinterpret_cast<const float *>(rec),
                                rec + 4 * K, V, dim, k, out, carry, carry_row, owner, esel,
-                               (const float *)nullptr, 0);
+                               (const float *)nullptr, 0, MAXK_F32);
             int rc = launch_status();
             if (rc) return rc;
             return fwd_fixup(sched, P, carry, owner, carry_row, out, dim, false, st);
@@ -3821,7 +4118,8 @@ struct FwdRecords {
             hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kBlock), fwd_lds_bytes<K>(k), st,
                                reinterpret_cast<const int2 *>(sched), P, indptr, idx, val,
                                reinterpret_cast<const float *>(rec), rec + 4 * K, V, dim, k, out,
-                               carry, carry_row, owner, (uint8_t *)nullptr, (const float *)nullptr, 0);
+                               carry, carry_row, owner, (uint8_t *)nullptr, (const float *)nullptr, 0,
+                               MAXK_F32);
             int rc = launch_status();
             if (rc) return rc;
             return fwd_fixup(sched, P, carry, owner, carry_row, out, dim, acc, st);
@@ -3991,6 +4289,47 @@ struct BwdSegsum {
         return launch_status();
     }
 };
+
+// STAGED backward of maxk_sspmm_backward_t: phase 1 reading gradient rows of
+// storage type TG, phase 2 writing a dXs of the run-time type odt (2-byte: the
+// owner-slot segmented sum; fp32: the fp32 path's phase 2, BwdSegsum).
+template <int K, typename TG>
+int bwd_stage_typed(const int32_t *sched, int64_t P, const int32_t *indptr, const int32_t *idx,
+                    const float *val, const void *grad, const uint8_t *sel,
+                    const int32_t *csc_pos, int V, int dim, int k, float *Pbuf, hipStream_t st)
+{
+    hipLaunchKernelGGL((bwd_panel_kernel<K, true, false, kPmCsc, TG>),
+                       dim3((unsigned)ceil_div(P, kWavesPerBlock)), dim3(kBlock), row_lds_bytes(),
+                       st, reinterpret_cast<const int2 *>(sched), P, indptr, idx, val,
+                       static_cast<const TG *>(grad), sel, csc_pos, V, dim, k, (float *)nullptr,
+                       Pbuf);
+    return launch_status();
+}
+
+template <int K>
+int bwd_segsum_typed(const int32_t *csched, int64_t CP, const int32_t *cptr, const float *Pbuf,
+                     int V, int k, void *dxs, int odt, float *carry, int32_t *carry_row,
+                     float *owner, hipStream_t st)
+{
+    const int64_t blocks = ceil_div(CP, kWavesPerBlock);
+    hipLaunchKernelGGL(bwd_segsum_owner_kernel<K>, dim3((unsigned)blocks), dim3(kBlock), 0, st,
+                       reinterpret_cast<const int2 *>(csched), CP, cptr, Pbuf, V, k, dxs, odt, carry,
+                       carry_row, owner);
+    int rc = launch_status();
+    if (rc) return rc;
+    hipLaunchKernelGGL(bwd_fixup_owner_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st,
+                       reinterpret_cast<const int2 *>(csched), CP, carry, owner, carry_row, dxs, odt,
+                       k);
+    return launch_status();
+}
+
+// compile-time k in {8, 16, 32, 64}, any other k generic (the *_t instantiation list)
+#define MAXK_TYPED_K(k, F, ...)                      \
+    ((k) == 8    ? F<8, ##__VA_ARGS__>               \
+     : (k) == 16 ? F<16, ##__VA_ARGS__>              \
+     : (k) == 32 ? F<32, ##__VA_ARGS__>              \
+     : (k) == 64 ? F<64, ##__VA_ARGS__>              \
+                 : F<0, ##__VA_ARGS__>)
 
 // APPEND backward (MAXK_BWD_APPEND): per-graph plan = the region base of every
 // (bin, XCD group); per call: cursors reset, phase 1 (single relation, node or
@@ -4279,6 +4618,56 @@ int maxk_spgemm_forward_sum_parts(const int32_t *sched, int64_t num_panels, cons
                                 as_stream(stream), (uint8_t *)nullptr,
                                 (flags & MAXK_FWD_CACHED_GATHER) != 0,
                                 num_parts > 0 ? parts : (const float *)nullptr, num_parts);
+}
+
+int maxk_spgemm_forward_t(const int32_t *sched, int64_t num_panels, const int32_t *indptr,
+                          const int32_t *indices, const float *values, const void *cbsr_data,
+                          int data_dtype, const uint8_t *cbsr_sel, int num_rows, int dim_origin,
+                          int dim_k, int flags, const float *parts, int num_parts, void *out,
+                          int out_dtype, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!dtype_ok(data_dtype) || !dtype_ok(out_dtype)) return MAXK_E_ARG;
+    if (flags & ~(MAXK_FWD_ACCUMULATE | MAXK_FWD_CACHED_GATHER)) return MAXK_E_ARG;
+    const bool acc = (flags & MAXK_FWD_ACCUMULATE) != 0;
+    // a 2-byte row would be rounded, added to and rounded again; the fused sum
+    // of parts overwrites
+    if (acc && (out_dtype != MAXK_F32 || num_parts != 0)) return MAXK_E_ARG;
+    if (num_parts < 0 || (num_parts > 0 && !parts)) return MAXK_E_ARG;
+    if (!aligned16(cbsr_data) || !aligned16(cbsr_sel) || !aligned16(out) || !aligned16(parts) ||
+        !aligned16(workspace))
+        return MAXK_E_ARG;
+    if (data_dtype == MAXK_F32 && out_dtype == MAXK_F32) {  // the fp32 kernels, unchanged
+        const float *d = static_cast<const float *>(cbsr_data);
+        float *o = static_cast<float *>(out);
+        if (acc)
+            return maxk_spgemm_forward_ex(sched, num_panels, indptr, indices, values, d, cbsr_sel,
+                                          num_rows, dim_origin, dim_k, flags, o, workspace,
+                                          workspace_bytes, stream);
+        return maxk_spgemm_forward_sum_parts(sched, num_panels, indptr, indices, values, d, cbsr_sel,
+                                             num_rows, dim_origin, dim_k, flags, parts, num_parts,
+                                             o, workspace, workspace_bytes, stream);
+    }
+    if (acc) return MAXK_E_ARG;  // fp32 out over 2-byte data: not built (multi-GPU halo path only)
+    if (!sched || !indptr || !out || num_panels < 1 || num_rows < 0) return MAXK_E_ARG;
+    if (!dims_ok(dim_origin, dim_k)) return MAXK_E_DIM;
+    if (num_rows == 0) return MAXK_OK;
+    if (!indices || !values || !cbsr_data || !cbsr_sel) return MAXK_E_ARG;
+    if (!workspace || workspace_bytes < maxk_forward_workspace_bytes(num_panels, dim_origin))
+        return MAXK_E_WORKSPACE;
+    const size_t dimp = (size_t)((dim_origin + 3) & ~3);
+    float *carry = static_cast<float *>(workspace);
+    int32_t *carry_row = reinterpret_cast<int32_t *>(
+        static_cast<char *>(workspace) + align_up((size_t)num_panels * dimp * sizeof(float), 256));
+    float *owner = fwd_owner_slots(workspace, num_panels, dim_origin);
+    const bool cached = (flags & MAXK_FWD_CACHED_GATHER) != 0;
+    const float *sump = num_parts > 0 ? parts : (const float *)nullptr;
+#define MAXK_FWD_T_ARGS dim_k, sched, num_panels, indptr, indices, values, cbsr_data, cbsr_sel, \
+        num_rows, dim_origin, dim_k, out, out_dtype, carry, carry_row, owner, as_stream(stream), \
+        cached, sump, num_parts
+    if (data_dtype == MAXK_F16) return fwd_typed_k<f16_t>(MAXK_FWD_T_ARGS);
+    if (data_dtype == MAXK_BF16) return fwd_typed_k<bf16_t>(MAXK_FWD_T_ARGS);
+    return fwd_typed_k<float>(MAXK_FWD_T_ARGS);
+#undef MAXK_FWD_T_ARGS
 }
 
 int maxk_rows_sum(const float *parts, int num_parts, int64_t n, float *out, void *stream)
@@ -4598,6 +4987,89 @@ int maxk_sspmm_backward(int algo, const int32_t *sched, int64_t num_panels,
     return dispatch_k<BwdSegsum>(dim_k, csc_sched, csc_num_panels, csc_indptr, Pbuf, num_cols,
                                  dim_k, dxs, carry, carry_row, st,
                                  gather ? csc_pos : (const int32_t *)nullptr);
+}
+
+size_t maxk_backward_workspace_bytes_t(int algo, int64_t num_edges, int dim_k,
+                                       int64_t csc_num_panels, int dxs_dtype)
+{
+    const size_t base = maxk_backward_workspace_bytes(algo, num_edges, dim_k, csc_num_panels);
+    if (dxs_dtype == MAXK_F32 || algo == MAXK_BWD_ATOMIC) return base;
+    // + the owner parts of split destinations (bwd_segsum_owner_kernel)
+    return base + align_up((size_t)csc_num_panels * dim_k * sizeof(float), 256);
+}
+
+int maxk_sspmm_backward_t(int algo, const int32_t *sched, int64_t num_panels,
+                          const int32_t *indptr, const int32_t *indices, const float *values,
+                          const void *grad, int grad_dtype, const uint8_t *cbsr_sel, int num_rows,
+                          int num_cols, int64_t num_edges, int dim_origin, int dim_k, void *dxs,
+                          int dxs_dtype, const int32_t *csc_pos, const int32_t *csc_sched,
+                          int64_t csc_num_panels, const int32_t *csc_indptr, void *workspace,
+                          size_t workspace_bytes, void *stream)
+{
+    if (!dtype_ok(grad_dtype) || !dtype_ok(dxs_dtype)) return MAXK_E_ARG;
+    if (!aligned16(grad) || !aligned16(cbsr_sel) || !aligned16(dxs) || !aligned16(workspace))
+        return MAXK_E_ARG;
+    if (grad_dtype == MAXK_F32 && dxs_dtype == MAXK_F32)  // the fp32 kernels, unchanged
+        return maxk_sspmm_backward(algo, sched, num_panels, indptr, indices, values,
+                                   static_cast<const float *>(grad), cbsr_sel, num_rows, num_cols,
+                                   num_edges, dim_origin, dim_k, static_cast<float *>(dxs), csc_pos,
+                                   csc_sched, csc_num_panels, csc_indptr, workspace, workspace_bytes,
+                                   stream);
+    const bool staged_ready = csc_pos && csc_sched && csc_indptr && csc_num_panels >= 1 &&
+                              workspace;
+    // a 2-byte type runs STAGED only (AUTO: when its inputs are there)
+    if (algo == MAXK_BWD_AUTO && staged_ready) algo = MAXK_BWD_STAGED;
+    if (algo != MAXK_BWD_STAGED || !staged_ready) return MAXK_E_ARG;
+    if (!sched || !indptr || !dxs || num_panels < 1 || num_rows < 0 || num_cols < 0 ||
+        num_edges < 0)
+        return MAXK_E_ARG;
+    if (!dims_ok(dim_origin, dim_k)) return MAXK_E_DIM;
+    hipStream_t st = as_stream(stream);
+    if (num_cols == 0) return MAXK_OK;
+    if (num_rows == 0 || num_edges == 0) {  // no edge: dXs = 0 (all-zero bits in every type)
+        const size_t bytes = (size_t)num_cols * dim_k * dtype_bytes(dxs_dtype);
+        const int e = zero_floats(static_cast<float *>(dxs), bytes / 4, st);
+        if (e || bytes % 4 == 0) return e;
+        // an odd count of 2-byte elements: the last one (a kernel, as zero_kernel: no memset node)
+        hipLaunchKernelGGL(zero_u16_kernel, dim3(1), dim3(kWave), 0, st,
+                           static_cast<uint16_t *>(dxs) + bytes / 2 - 1, (size_t)1);
+        return launch_status();
+    }
+    if (!indices || !values || !grad || !cbsr_sel) return MAXK_E_ARG;
+    if (workspace_bytes < maxk_backward_workspace_bytes_t(MAXK_BWD_STAGED, num_edges, dim_k,
+                                                          csc_num_panels, dxs_dtype))
+        return MAXK_E_WORKSPACE;
+    // workspace: [P rows (E*kp floats)] [carry (CP*k floats)] [carry_row (CP ints)] [owner (CP*k)]
+    const int kp = dim_k == 8 ? 16 : dim_k;
+    const size_t pbytes = align_up((size_t)num_edges * kp * sizeof(float), 256);
+    const size_t carry_bytes = align_up((size_t)csc_num_panels * dim_k * sizeof(float), 256);
+    char *wsb = static_cast<char *>(workspace);
+    float *Pbuf = static_cast<float *>(workspace);
+    float *carry = reinterpret_cast<float *>(wsb + pbytes);
+    int32_t *carry_row = reinterpret_cast<int32_t *>(wsb + pbytes + carry_bytes);
+    float *owner = reinterpret_cast<float *>(
+        wsb + pbytes + carry_bytes + align_up((size_t)csc_num_panels * sizeof(int32_t), 256));
+    int rc;
+    if (grad_dtype == MAXK_F16)
+        rc = MAXK_TYPED_K(dim_k, bwd_stage_typed, f16_t)(
+            sched, num_panels, indptr, indices, values, grad, cbsr_sel, csc_pos, num_rows,
+            dim_origin, dim_k, Pbuf, st);
+    else if (grad_dtype == MAXK_BF16)
+        rc = MAXK_TYPED_K(dim_k, bwd_stage_typed, bf16_t)(
+            sched, num_panels, indptr, indices, values, grad, cbsr_sel, csc_pos, num_rows,
+            dim_origin, dim_k, Pbuf, st);
+    else  // fp32 gradient rows, 2-byte dXs: the fp32 phase 1
+        rc = dispatch_k<BwdPanel>(dim_k, true, sched, num_panels, indptr, indices, values,
+                                  static_cast<const float *>(grad), cbsr_sel, csc_pos, num_rows,
+                                  dim_origin, dim_k, (float *)nullptr, Pbuf, st, false, kPmCsc);
+    if (rc) return rc;
+    if (dxs_dtype == MAXK_F32)
+        return dispatch_k<BwdSegsum>(dim_k, csc_sched, csc_num_panels, csc_indptr, Pbuf, num_cols,
+                                     dim_k, static_cast<float *>(dxs), carry, carry_row, st,
+                                     (const int32_t *)nullptr);
+    return MAXK_TYPED_K(dim_k, bwd_segsum_typed)(csc_sched, csc_num_panels, csc_indptr, Pbuf,
+                                                 num_cols, dim_k, dxs, dxs_dtype, carry, carry_row,
+                                                 owner, st);
 }
 
 // Validation, workspace carve-up and phase 2 (the CSC segmented sum) of the

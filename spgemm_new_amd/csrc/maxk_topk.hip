@@ -29,8 +29,11 @@
 #include <stdint.h>
 
 #include "../../include/maxk_spgemm.h"
+#include "maxk_types.h"
 
 namespace {
+
+using namespace maxk;
 
 constexpr int kWave = 64;
 constexpr int kWavesPerBlock = 4;
@@ -80,40 +83,51 @@ __device__ __forceinline__ int lane_order_pos(int q, int k)
     return vec * (q % lpe) + q / lpe;
 }
 
-template <int ORDER>
-__global__ __launch_bounds__(kBlock) void topk_kernel(const float *__restrict__ x, int num_rows,
+// E: the storage type (float, f16_t, bf16_t).  A 2-byte row is loaded as one
+// 8-byte word per lane and ranked by the fp32 keys of its up-cast entries (the
+// up-cast is exact and monotonic, so the selection is the fp32 kernel's on
+// x.float()); what is stored is the entry itself, bit for bit.
+template <int ORDER, typename E = float>
+__global__ __launch_bounds__(kBlock) void topk_kernel(const E *__restrict__ x, int num_rows,
                                                       int dim, int64_t ld, int k,
-                                                      float *__restrict__ data,
+                                                      E *__restrict__ data,
                                                       uint8_t *__restrict__ sel,
-                                                      float *__restrict__ dense)
+                                                      E *__restrict__ dense)
 {
+    constexpr bool HALF = sizeof(E) == 2;
     __shared__ uint64_t stage[kWavesPerBlock][kMaxDim];  // value order: (key << 32 | ~col)
     const int lane = threadIdx.x & (kWave - 1);
     const int wl = threadIdx.x / kWave;
     const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
     const bool vec = (dim & 3) == 0 && (ld & 3) == 0;
-    auto load_row = [&](int64_t rr, float *v) {
-        const float *row = x + rr * ld;
+    auto load_row = [&](int64_t rr, E *v) {
+        const E *row = x + rr * ld;
         if (vec && 4 * lane < dim) {
-            const float4 q = *reinterpret_cast<const float4 *>(row + 4 * lane);
-            v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+            if constexpr (HALF) {
+                const u32x2 q = *reinterpret_cast<const u32x2 *>(row + 4 * lane);
+                v[0].u = (uint16_t)q.x; v[1].u = (uint16_t)(q.x >> 16);
+                v[2].u = (uint16_t)q.y; v[3].u = (uint16_t)(q.y >> 16);
+            } else {
+                const float4 q = *reinterpret_cast<const float4 *>(row + 4 * lane);
+                v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+            }
         } else {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = (4 * lane + j < dim) ? row[4 * lane + j] : 0.f;
+            for (int j = 0; j < 4; ++j) v[j] = (4 * lane + j < dim) ? row[4 * lane + j] : E{};
         }
     };
     int64_t r = (int64_t)blockIdx.x * kWavesPerBlock + wl;
     uint32_t prevT = 0xbf800000u;  // key of 1.0f: a start for the first row
-    float nx[4] = {0.f, 0.f, 0.f, 0.f};
+    E nx[4] = {E{}, E{}, E{}, E{}};
     if (r < num_rows) load_row(r, nx);
     for (; r < num_rows; r += nwaves) {
-        float v[4];
+        E v[4];
         uint32_t key[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = nx[j];
         if (r + nwaves < num_rows) load_row(r + nwaves, nx);  // next row in flight
 #pragma unroll
-        for (int j = 0; j < 4; ++j) key[j] = (4 * lane + j < dim) ? float_key(v[j]) : 0u;
+        for (int j = 0; j < 4; ++j) key[j] = (4 * lane + j < dim) ? float_key(load_f32(&v[j])) : 0u;
         // T = the largest key value with #{key >= T} >= k (the k-th largest key),
         // or any T with exactly k keys >= T (then those k are the selection).
         // Search: bracket [lo, hi) with count(lo) >= k > count(hi), found by
@@ -194,7 +208,7 @@ __global__ __launch_bounds__(kBlock) void topk_kernel(const float *__restrict__ 
         int pos = 0;
 #pragma unroll
         for (int j = 0; j < 4; ++j) pos += prefix_count(sm[j]);
-        float *drow = data + r * (int64_t)k;
+        E *drow = data + r * (int64_t)k;
         uint8_t *srow = sel + r * (int64_t)k;
         if constexpr (ORDER != MAXK_TOPK_ORDER_VALUE) {
 #pragma unroll
@@ -257,33 +271,45 @@ __global__ __launch_bounds__(kBlock) void topk_kernel(const float *__restrict__ 
             wave_sync_lds();
         }
         if (dense) {
-            float *orow = dense + r * (int64_t)dim;
+            E *orow = dense + r * (int64_t)dim;
+            if constexpr (HALF) {
+                if ((dim & 3) == 0) {  // the lane's four elements as one 8-byte store
+                    if (4 * lane < dim) {
+                        u32x2 q;
+                        q.x = (take[0] ? v[0].u : 0u) | ((take[1] ? (uint32_t)v[1].u : 0u) << 16);
+                        q.y = (take[2] ? v[2].u : 0u) | ((take[3] ? (uint32_t)v[3].u : 0u) << 16);
+                        *reinterpret_cast<u32x2 *>(orow + 4 * lane) = q;
+                    }
+                    continue;
+                }
+            }
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                if (4 * lane + j < dim) orow[4 * lane + j] = take[j] ? v[j] : 0.f;
+                if (4 * lane + j < dim) orow[4 * lane + j] = take[j] ? v[j] : E{};
         }
     }
 }
 
 // DENSE_SRC: vals is a dense [num_rows, dim] array read at the selected
 // columns (MaxK backward: grad masked to the top-k), else [num_rows, k].
-template <bool DENSE_SRC>
-__global__ __launch_bounds__(kBlock) void scatter_kernel(const float *__restrict__ vals,
+// E: float, or uint16_t for both 2-byte types (a move: the bits are not looked at).
+template <bool DENSE_SRC, typename E = float>
+__global__ __launch_bounds__(kBlock) void scatter_kernel(const E *__restrict__ vals,
                                                          const uint8_t *__restrict__ sel,
                                                          int num_rows, int k, int dim,
-                                                         float *__restrict__ out)
+                                                         E *__restrict__ out)
 {
-    typedef float f4v __attribute__((ext_vector_type(4)));
-    __shared__ __attribute__((aligned(16))) float rowbuf[kWavesPerBlock][kMaxDim];
+    typedef E f4v __attribute__((ext_vector_type(4)));  // a lane's four elements: 16 or 8 bytes
+    __shared__ __attribute__((aligned(16))) E rowbuf[kWavesPerBlock][kMaxDim];
     const int lane = threadIdx.x & (kWave - 1);
     const int wl = threadIdx.x / kWave;
-    float *rb = rowbuf[wl];
+    E *rb = rowbuf[wl];
     const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
     const bool vec = (dim & 3) == 0;
     // the dense row leaves as one 16-B non-temporal store per lane (written
     // once, never re-read here: Reddit 0.060 -> 0.039 ms)
     auto store_row = [&](int64_t r) {
-        float *orow = out + r * (int64_t)dim;
+        E *orow = out + r * (int64_t)dim;
         if (vec) {
             if (4 * lane < dim)
                 __builtin_nontemporal_store(reinterpret_cast<const f4v *>(rb)[lane],
@@ -294,9 +320,9 @@ __global__ __launch_bounds__(kBlock) void scatter_kernel(const float *__restrict
     };
     auto zero_row = [&]() {
         if (vec) {
-            if (4 * lane < dim) reinterpret_cast<f4v *>(rb)[lane] = f4v{0.f, 0.f, 0.f, 0.f};
+            if (4 * lane < dim) reinterpret_cast<f4v *>(rb)[lane] = f4v{E(0), E(0), E(0), E(0)};
         } else {
-            for (int i = lane; i < dim; i += kWave) rb[i] = 0.f;
+            for (int i = lane; i < dim; i += kWave) rb[i] = E(0);
         }
     };
     int64_t r = (int64_t)blockIdx.x * kWavesPerBlock + wl;
@@ -304,20 +330,20 @@ __global__ __launch_bounds__(kBlock) void scatter_kernel(const float *__restrict
         // one entry per lane; the next row's entries are loaded while this row
         // is assembled and stored (one row in flight per wave was latency-bound:
         // products 3.4 TB/s of rows written)
-        auto fetch = [&](int64_t rr, int &c, float &v) {
+        auto fetch = [&](int64_t rr, int &c, E &v) {
             c = dim;
-            v = 0.f;
+            v = E(0);
             if (rr < num_rows && lane < k) {
                 c = sel[rr * k + lane];
                 if (!DENSE_SRC) v = vals[rr * k + lane];
             }
         };
         int nc;
-        float nv;
+        E nv;
         fetch(r, nc, nv);
         for (; r < num_rows; r += nwaves) {
             const int c = nc;
-            float v = nv;
+            E v = nv;
             fetch(r + nwaves, nc, nv);
             if (DENSE_SRC && c < dim) v = vals[r * (int64_t)dim + c];
             zero_row();
@@ -404,6 +430,89 @@ int maxk_cbsr_mask(const float *src, const uint8_t *cbsr_sel, int num_rows, int 
                        reinterpret_cast<hipStream_t>(stream), src, cbsr_sel, num_rows, k, dim,
                        out);
     return launch_status();
+}
+
+}  // extern "C"
+
+namespace {
+
+template <typename E>
+int topk_launch(const void *x, int num_rows, int dim, int64_t ld, int k, int order, void *data,
+                uint8_t *sel, void *dense, hipStream_t st)
+{
+    const dim3 g(grid_for(num_rows)), b(kBlock);
+    const E *xe = static_cast<const E *>(x);
+    E *de = static_cast<E *>(data), *oe = static_cast<E *>(dense);
+    if (order == MAXK_TOPK_ORDER_VALUE)
+        hipLaunchKernelGGL((topk_kernel<MAXK_TOPK_ORDER_VALUE, E>), g, b, 0, st, xe, num_rows, dim,
+                           ld, k, de, sel, oe);
+    else if (order == MAXK_TOPK_ORDER_LANE)
+        hipLaunchKernelGGL((topk_kernel<MAXK_TOPK_ORDER_LANE, E>), g, b, 0, st, xe, num_rows, dim,
+                           ld, k, de, sel, oe);
+    else
+        hipLaunchKernelGGL((topk_kernel<MAXK_TOPK_ORDER_COLUMN, E>), g, b, 0, st, xe, num_rows, dim,
+                           ld, k, de, sel, oe);
+    return launch_status();
+}
+
+// DENSE_SRC false: scatter, true: mask
+template <bool DENSE_SRC>
+int scatter_t(const void *vals, int dtype, const uint8_t *cbsr_sel, int num_rows, int k,
+                     int dim, void *out, void *stream)
+{
+    if (!dtype_ok(dtype)) return MAXK_E_ARG;
+    if (num_rows < 0 || (num_rows > 0 && (!vals || !cbsr_sel || !out))) return MAXK_E_ARG;
+    if (!aligned16(vals) || !aligned16(out)) return MAXK_E_ARG;
+    if (dim < 1 || dim > kMaxDim || k < 1 || k > dim) return MAXK_E_DIM;
+    if (num_rows == 0) return MAXK_OK;
+    const dim3 g(grid_for(num_rows)), b(kBlock);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (dtype == MAXK_F32)
+        hipLaunchKernelGGL((scatter_kernel<DENSE_SRC>), g, b, 0, st,
+                           static_cast<const float *>(vals), cbsr_sel, num_rows, k, dim,
+                           static_cast<float *>(out));
+    else
+        hipLaunchKernelGGL((scatter_kernel<DENSE_SRC, uint16_t>), g, b, 0, st,
+                           static_cast<const uint16_t *>(vals), cbsr_sel, num_rows, k, dim,
+                           static_cast<uint16_t *>(out));
+    return launch_status();
+}
+
+}  // namespace
+
+extern "C" {
+
+int maxk_topk_cbsr_t(const void *x, int dtype, int num_rows, int dim, int64_t ld, int k, int order,
+                     void *cbsr_data, uint8_t *cbsr_sel, void *dense_out, void *stream)
+{
+    if (!dtype_ok(dtype)) return MAXK_E_ARG;
+    if (num_rows < 0 || (num_rows > 0 && (!x || !cbsr_data || !cbsr_sel))) return MAXK_E_ARG;
+    if (!aligned16(x) || !aligned16(cbsr_data) || !aligned16(dense_out)) return MAXK_E_ARG;
+    if (dtype == MAXK_F32)
+        return maxk_topk_cbsr(static_cast<const float *>(x), num_rows, dim, ld, k, order,
+                              static_cast<float *>(cbsr_data), cbsr_sel,
+                              static_cast<float *>(dense_out), stream);
+    if (dim < 1 || dim > kMaxDim || k < 1 || k > dim || ld < dim) return MAXK_E_DIM;
+    if (order != MAXK_TOPK_ORDER_COLUMN && order != MAXK_TOPK_ORDER_VALUE &&
+        order != MAXK_TOPK_ORDER_LANE)
+        return MAXK_E_ARG;
+    if (num_rows == 0) return MAXK_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (dtype == MAXK_F16)
+        return topk_launch<f16_t>(x, num_rows, dim, ld, k, order, cbsr_data, cbsr_sel, dense_out, st);
+    return topk_launch<bf16_t>(x, num_rows, dim, ld, k, order, cbsr_data, cbsr_sel, dense_out, st);
+}
+
+int maxk_cbsr_scatter_t(const void *vals, int dtype, const uint8_t *cbsr_sel, int num_rows, int k,
+                        int dim, void *out, void *stream)
+{
+    return scatter_t<false>(vals, dtype, cbsr_sel, num_rows, k, dim, out, stream);
+}
+
+int maxk_cbsr_mask_t(const void *src, int dtype, const uint8_t *cbsr_sel, int num_rows, int k,
+                     int dim, void *out, void *stream)
+{
+    return scatter_t<true>(src, dtype, cbsr_sel, num_rows, k, dim, out, stream);
 }
 
 }  // extern "C"

@@ -104,8 +104,12 @@ class SpmmBase {
     {
         check_dev(input_features, "input_features");
         check_dev(output_features, "output_features");
-        TORCH_CHECK(input_features.dtype() == torch::kFloat32, "input_features must be float32");
-        TORCH_CHECK(output_features.dtype() == torch::kFloat32, "output_features must be float32");
+        TORCH_CHECK(input_features.dtype() == torch::kFloat32,
+                    "input_features must be float32 (this module is fp32 only; half-precision "
+                    "features run through spgemm_new_amd.MaxKGraph)");
+        TORCH_CHECK(output_features.dtype() == torch::kFloat32,
+                    "output_features must be float32 (this module is fp32 only; half-precision "
+                    "features run through spgemm_new_amd.MaxKGraph)");
         vin_ = input_features;
         vout_ = output_features;
     }

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .ops import MaxKGraph, check_tensor, topk_cbsr, warp4_build
+from .ops import MaxKGraph, check_tensor, fp32_only, topk_cbsr, warp4_build
 
 FULL_DIM = 256  # cuda_kernel_bindings.cpp:70
 
@@ -29,6 +29,7 @@ FULL_DIM = 256  # cuda_kernel_bindings.cpp:70
 def _warp4_checks(warp4_metadata, indices, values, input_data, sparse_selector):
     check_tensor(warp4_metadata, "warp4_metadata", torch.int32)
     check_tensor(indices, "indices", torch.int32)
+    fp32_only("spmm_maxk_forward (the warp4 drop-in)", input_data=input_data)
     check_tensor(values, "values", torch.float32)
     check_tensor(input_data, "input_data", torch.float32)
     check_tensor(sparse_selector, "sparse_selector", torch.uint8)
@@ -108,6 +109,7 @@ def spmm_maxk_backward(warp4_metadata, indices, values, grad_output, sparse_sele
     """cuda_kernel_bindings.cpp:106-161 -> fp32[V, dim_sparse]."""
     check_tensor(warp4_metadata, "warp4_metadata", torch.int32)
     check_tensor(indices, "indices", torch.int32)
+    fp32_only("spmm_maxk_backward (the warp4 drop-in)", grad_output=grad_output)
     check_tensor(values, "values", torch.float32)
     check_tensor(grad_output, "grad_output", torch.float32)
     check_tensor(sparse_selector, "sparse_selector", torch.uint8)

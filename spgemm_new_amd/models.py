@@ -11,32 +11,50 @@ Fixed relative to the reference: the kernel path actually runs,
 there is no per-layer debug copy, and the sparse->dense gradient scatter is a
 single device kernel instead of a V*k Python loop (utils/models.py:136-141).
 No fallback: if the HIP library is missing the call raises.
+
+``MaxK`` and ``SpGEMMFunction`` run in the dtype of their input -- float32,
+float16 or bfloat16 (fp32 sums inside, one rounding per output element) -- so
+under ``torch.autocast`` the aggregation takes and returns what ``nn.Linear``
+hands it, with no up- and down-cast around the call.  The multi-relation and
+partitioned Functions are fp32 only and say so.
 """
 from __future__ import annotations
 
 import torch
+from torch.amp import custom_bwd, custom_fwd
 from torch.autograd import Function
 
 from .graph_cache import graph_for
-from .ops import cbsr_mask, cbsr_scatter, topk_cbsr
+from .ops import cbsr_mask, cbsr_scatter, fp32_only, topk_cbsr
+
+
+def _grad_as(grad_output: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """The incoming gradient in the forward's dtype (autograd may hand over another
+    floating dtype, e.g. an fp32 gradient for a bf16 output)."""
+    if grad_output.dtype != dtype:
+        grad_output = grad_output.to(dtype)
+    return grad_output.contiguous()
 
 
 class MaxK(Function):
     """utils/models.py:28-59: keep the k largest entries per row; gradient masked."""
 
     @staticmethod
+    @custom_fwd(device_type="cuda")
     def forward(ctx, input, k=1):
         # the HIP producer's domain; no fallback outside it (a CPU or fp64 tensor raises)
         if input.dim() != 2 or input.size(1) > 256:
             raise RuntimeError("MaxK: input must be 2-D with at most 256 columns")
         _, sel, out = topk_cbsr(input.contiguous(), k, dense=True)
         ctx.save_for_backward(sel)
+        ctx.dtype = input.dtype
         return out
 
     @staticmethod
+    @custom_bwd(device_type="cuda")
     def backward(ctx, grad_output):
         (sel,) = ctx.saved_tensors
-        return cbsr_mask(grad_output.contiguous(), sel), None
+        return cbsr_mask(_grad_as(grad_output, ctx.dtype), sel), None
 
 
 def cbsr_topk(features: torch.Tensor, maxk: int, order: str = "value"):
@@ -49,6 +67,7 @@ class SpGEMMFunction(Function):
     """utils/models.py:61-149: forward Y = A . topk_k(X), backward mask . (A^T G)."""
 
     @staticmethod
+    @custom_fwd(device_type="cuda")
     def forward(ctx, features, graph_data, maxk):
         indptr, indices, values = graph_data
         if features.dim() != 2:
@@ -63,13 +82,15 @@ class SpGEMMFunction(Function):
         ctx.sparse_selector = sel
         ctx.maxk = maxk
         ctx.features_shape = x.shape
+        ctx.dtype = x.dtype
         return out
 
     @staticmethod
+    @custom_bwd(device_type="cuda")
     def backward(ctx, grad_output):
         g = ctx.graph
         sel = ctx.sparse_selector
-        dxs = g.backward(grad_output.contiguous(), sel)
+        dxs = g.backward(_grad_as(grad_output, ctx.dtype), sel)
         return cbsr_scatter(dxs, sel, ctx.features_shape[1]), None, None
 
 
@@ -83,6 +104,7 @@ class SpGEMMMultiFunction(Function):
     @staticmethod
     def forward(ctx, features, graph_data, values, maxk):
         indptr, indices = graph_data[0], graph_data[1]
+        fp32_only("SpGEMMMultiFunction", features=features, values=values)
         x = features.contiguous()
         data, sel = topk_cbsr(x, maxk, order="column")
         g = graph_for(indptr.contiguous(), indices.contiguous(), None)
@@ -114,6 +136,7 @@ class PartitionedSpGEMMFunction(Function):
     def forward(ctx, features_own, model, maxk):
         if features_own.dim() != 2 or features_own.shape[0] != model.plan.num_own:
             raise RuntimeError("features must be the rank's own rows [num_own, h]")
+        fp32_only("PartitionedSpGEMMFunction", features=features_own)
         x = features_own.contiguous()
         data, sel = topk_cbsr(x, maxk, order="column")
         out = model.forward(data, sel, x.size(1))
@@ -142,6 +165,7 @@ class PartitionedSpGEMMMultiFunction(Function):
     def forward(ctx, features_own, model, maxk):
         if features_own.dim() != 2 or features_own.shape[0] != model.plan.num_own:
             raise RuntimeError("features must be the rank's own rows [num_own, h]")
+        fp32_only("PartitionedSpGEMMMultiFunction", features=features_own)
         x = features_own.contiguous()
         data, sel = topk_cbsr(x, maxk, order="column")
         out = model.forward_multi(data, sel, x.size(1))

@@ -49,6 +49,32 @@ def check_tensor(t, name: str, dtype=None, cuda: bool = True, dim: int | None = 
     return t
 
 
+HALF_DTYPES = (torch.float16, torch.bfloat16)
+
+
+def check_feature(t, name: str, dim: int | None = None, like: torch.Tensor | None = None):
+    """A feature array (CBSR data, output, gradient): float32, float16 or bfloat16.
+    like: the array whose dtype it has to share -- the kernels keep one storage
+    type per call, so a caller's ``out`` of another dtype (fp16 with bf16, half
+    with fp32) is refused rather than converted."""
+    check_tensor(t, name, None, dim=dim)
+    if _lib.dtype_code(t.dtype) is None:
+        raise RuntimeError(f"{name} must be float32, float16 or bfloat16, got {t.dtype}")
+    if like is not None and t.dtype != like.dtype:
+        raise RuntimeError(f"{name} must have the dtype of its input ({like.dtype}), got {t.dtype}")
+    return t
+
+
+def fp32_only(what: str, **tensors):
+    """The paths that have no half-precision kernels (multi-relation, partitioned,
+    records / packed, warp4 drop-ins) say so instead of failing on a dtype check."""
+    for name, t in tensors.items():
+        if t is not None and t.dtype in HALF_DTYPES:
+            raise RuntimeError(f"{what} is fp32 only: {name} is {t.dtype}; half-precision features "
+                               "run through MaxKGraph.forward / backward, topk_cbsr, cbsr_scatter "
+                               "and cbsr_mask")
+
+
 def _stream(t):
     return _lib.stream_ptr(t.device)
 
@@ -695,8 +721,10 @@ class MaxKGraph:
     def forward(self, cbsr_data: torch.Tensor, cbsr_sel: torch.Tensor, dim_origin: int = 256,
                 out: torch.Tensor | None = None, values: torch.Tensor | None = None,
                 accumulate: bool = False, edge_sel: bool | str = False) -> torch.Tensor:
-        """Y = A . scatter(CBSR)  (spmm_maxk.cu:17-106).  Returns fp32[V, dim_origin];
-        accumulate=True adds into out instead.  edge_sel: also write the edge
+        """Y = A . scatter(CBSR)  (spmm_maxk.cu:17-106).  Returns [V, dim_origin] in
+        cbsr_data's dtype (float32, float16 or bfloat16; fp32 sums, a half output
+        rounded once; half features take the plain or column-blocked forward);
+        accumulate=True (fp32 only) adds into out instead.  edge_sel: also write the edge
         selectors for a STAGED_EDGE / EDGE_GATHER backward of this same selector
         tensor -- "auto": when AUTO chose such a backward for (k, h); only a
         caller that runs that backward next should ask (the autograd Function
@@ -733,6 +761,7 @@ class MaxKGraph:
         single-relation calls (per-relation value columns cached), summed on the
         device.  AUTO times the fused candidates once per (k, h, R) (MAXK_AUTO=
         fixed: MULTI_STAGED when it applies, then LOCAL rel8, else composed)."""
+        fp32_only("the multi-relation backward", grad_output=grad, grad_input=out)
         check_tensor(grad, "grad_output", torch.float32, dim=3)
         check_tensor(values, "values", torch.float32, dim=2)
         R = values.shape[1]
@@ -959,7 +988,8 @@ class MaxKGraph:
 
     def backward(self, grad: torch.Tensor, cbsr_sel: torch.Tensor, out: torch.Tensor | None = None,
                  values: torch.Tensor | None = None, algo: int = _lib.MAXK_BWD_AUTO) -> torch.Tensor:
-        """dXs = (A^T G) sampled at sel  (spmm_maxk_backward.cu:15-115).  Returns fp32[V, k]."""
+        """dXs = (A^T G) sampled at sel  (spmm_maxk_backward.cu:15-115).  Returns [V, k]
+        in grad's dtype (float32, float16 or bfloat16; half gradients run STAGED)."""
         return sspmm_backward(self, grad, cbsr_sel, out, values, algo)
 
 
@@ -980,8 +1010,11 @@ def _check_values(g: MaxKGraph, values):
     return values if g.num_edges > 0 else g.values
 
 
-def _check_cbsr(g: MaxKGraph, data, sel):
-    check_tensor(data, "input_data", torch.float32, dim=2)
+def _check_cbsr(g: MaxKGraph, data, sel, half_ok: bool = False):
+    if half_ok:
+        check_feature(data, "input_data", dim=2)
+    else:
+        check_tensor(data, "input_data", torch.float32, dim=2)
     check_tensor(sel, "sparse_selector", torch.uint8, dim=2)
     if data.shape != sel.shape:
         raise RuntimeError("input_data and sparse_selector must have the same shape")
@@ -996,23 +1029,42 @@ def spgemm_forward(g: MaxKGraph, data, sel, dim_origin: int = 256, out=None, val
     """edge_sel: also write the edge selectors of sel (kept by the graph for the
     STAGED_EDGE / EDGE_GATHER backward); "auto" = when AUTO chose such a backward
     for (k, h)."""
-    _check_cbsr(g, data, sel)
+    _check_cbsr(g, data, sel, half_ok=True)
     k = data.shape[1]
     values = _check_values(g, values)
+    half = data.dtype in HALF_DTYPES
     if out is None:
         if accumulate:
             raise RuntimeError("accumulate needs an output")
-        out = torch.empty((g.num_rows, dim_origin), dtype=torch.float32, device=g.device)
+        out = torch.empty((g.num_rows, dim_origin), dtype=data.dtype, device=g.device)
     else:
-        check_tensor(out, "output", torch.float32, dim=2)
+        check_feature(out, "output", dim=2, like=data)
         if tuple(out.shape) != (g.num_rows, dim_origin):
             raise RuntimeError("output has the wrong shape")
         _on_device(g, output=out)
+    if half and accumulate:
+        raise RuntimeError("accumulate is fp32 only: a half-precision output would be rounded, "
+                           "added to and rounded again")
+    if half and edge_sel is True:
+        raise RuntimeError("the edge-selector forward is fp32 only (half-precision features run "
+                           "the plain or column-blocked forward and the STAGED backward)")
     if g.num_rows == 0:
         return out   # an empty block (a rank of the row partition that owns no row)
     if g.num_cols == 0:
         return out if accumulate else out.zero_()   # no source nodes: Y = 0
     L = _lib.load()
+    if half:
+        # no packed-record or edge-selector form: plain, or column-blocked where
+        # _fwd_blocks chooses it for the shape
+        if k >= 32 and g.num_edges > 0:
+            nb = _fwd_blocks(g, data, sel, dim_origin, out, values)
+            if nb:
+                return _forward_blocked(g, nb, data, sel, dim_origin, out, values)
+        ws = g._workspace(("fwd", dim_origin),
+                          L.maxk_forward_workspace_bytes(g.num_panels, dim_origin))
+        return _forward_typed(g.sched, g.num_panels, g.indptr, g.indices, values, data, sel,
+                              g.num_rows, dim_origin, 0, None, 0, out, ws,
+                              "maxk_spgemm_forward_t")
     nbytes = L.maxk_forward_workspace_bytes(g.num_panels, dim_origin)
     ws = g._workspace(("fwd", dim_origin), nbytes)
     if edge_sel == "auto":
@@ -1048,6 +1100,19 @@ def spgemm_forward(g: MaxKGraph, data, sel, dim_origin: int = 256, out=None, val
                                         sel.data_ptr(), g.num_rows, dim_origin, k, flags,
                                         out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(out)),
                "maxk_spgemm_forward")
+    return out
+
+
+def _forward_typed(sched, P, indptr, indices, values, data, sel, num_rows, dim_origin, flags,
+                   parts, num_parts, out, ws, what):
+    """maxk_spgemm_forward_t: the forward with the storage types of data and out
+    (fp32 partials in ``parts``; all-fp32 arguments run the fp32 kernels)."""
+    L = _lib.load()
+    _lib.check(L.maxk_spgemm_forward_t(
+        sched.data_ptr(), P, indptr.data_ptr(), indices.data_ptr(), values.data_ptr(),
+        data.data_ptr(), _lib.dtype_code(data.dtype), sel.data_ptr(), num_rows, dim_origin,
+        data.shape[1], flags, _lib.ptr(parts), num_parts, out.data_ptr(),
+        _lib.dtype_code(out.dtype), ws.data_ptr(), ws.numel(), _stream(out)), what)
     return out
 
 
@@ -1088,6 +1153,19 @@ def _forward_blocked(g: MaxKGraph, nb: int, data, sel, dim_origin: int, out, val
     n = g.num_rows * dim_origin
     k = data.shape[1]
     parts = None
+    if data.dtype in HALF_DTYPES:
+        # blocks 0..nb-2 into the fp32 partials, then the last block, whose row flush
+        # adds them and rounds each output element once
+        if nb > 1:
+            parts = g._workspace(("fwd_parts", nb, dim_origin), 4 * (nb - 1) * n)
+            pv = parts[: 4 * (nb - 1) * n].view(torch.float32)
+            _forward_typed(sp["head_sched"], sp["head_P"], plan["indptr"], plan["indices"], vals,
+                           data, sel, sp["head_rows"], dim_origin, _lib.MAXK_FWD_CACHED_GATHER,
+                           None, 0, pv, ws, "maxk_spgemm_forward_t (column-blocked, blocks 0..nb-2)")
+        return _forward_typed(sp["last_sched"], sp["last_P"], sp["last_indptr"], plan["indices"],
+                              vals, data, sel, g.num_rows, dim_origin,
+                              _lib.MAXK_FWD_CACHED_GATHER, parts, nb - 1, out, ws,
+                              "maxk_spgemm_forward_t (column-blocked, last block)")
     if nb > 1:
         parts = g._workspace(("fwd_parts", nb, dim_origin), 4 * (nb - 1) * n)
         _lib.check(L.maxk_spgemm_forward_ex(sp["head_sched"].data_ptr(), sp["head_P"],
@@ -1111,7 +1189,8 @@ def _fwd_blocks(g: MaxKGraph, data, sel, dim_origin: int, out, values) -> int:
     against the plain forward (graphs with long rows only; never under capture)."""
     if FWD_BLOCKS >= 0:
         return FWD_BLOCKS
-    key = (data.shape[1], dim_origin)
+    half = data.dtype in HALF_DTYPES
+    key = (data.shape[1], dim_origin, data.dtype) if half else (data.shape[1], dim_origin)
     nb = g._fwd_blocks.get(key)
     if nb is not None:
         return nb
@@ -1133,6 +1212,10 @@ def _fwd_blocks(g: MaxKGraph, data, sel, dim_origin: int, out, values) -> int:
     ws = g._workspace(("fwd", dim_origin), L.maxk_forward_workspace_bytes(g.num_panels, dim_origin))
 
     def plain():
+        if half:
+            return _forward_typed(g.sched, g.num_panels, g.indptr, g.indices, values, data, sel,
+                                  g.num_rows, dim_origin, 0, None, 0, out, ws,
+                                  "maxk_spgemm_forward_t")
         _lib.check(L.maxk_spgemm_forward_ex(g.sched.data_ptr(), g.num_panels, g.indptr.data_ptr(),
                                             g.indices.data_ptr(), values.data_ptr(),
                                             data.data_ptr(), sel.data_ptr(), g.num_rows,
@@ -1140,6 +1223,8 @@ def _fwd_blocks(g: MaxKGraph, data, sel, dim_origin: int, out, values) -> int:
                                             ws.data_ptr(), ws.numel(), _stream(out)),
                    "maxk_spgemm_forward")
     def drop(c):  # what a losing candidate built
+        if c in g._fwd_blocks.values():
+            return  # another shape or dtype of this graph runs with c blocks
         g._blocked.pop(c, None)
         g._ws.pop(("fwd_parts", c, dim_origin), None)
         g._ws.pop(("fwd_blocked", c, dim_origin), None)
@@ -1164,6 +1249,7 @@ def cbsr_gather_records(data: torch.Tensor, sel: torch.Tensor, rows: torch.Tenso
                         out: torch.Tensor | None = None) -> torch.Tensor:
     """Halo records: uint8[n, 5k], record i = (data[rows[i]] as k fp32, sel[rows[i]]).
     The multi-GPU all-to-all-v message (maxk_cbsr_gather_records)."""
+    fp32_only("cbsr_gather_records (halo records)", input_data=data)
     check_tensor(data, "input_data", torch.float32, dim=2)
     check_tensor(sel, "sparse_selector", torch.uint8, dim=2)
     if data.shape != sel.shape or data.device != sel.device:
@@ -1192,6 +1278,7 @@ def spgemm_forward_records(g: MaxKGraph, records: torch.Tensor, k: int, dim_orig
                            out=None, values=None, accumulate: bool = False):
     """Forward reading the CBSR from halo records (uint8[num_cols, 5k]);
     accumulate=True adds into out (maxk_spgemm_forward_records)."""
+    fp32_only("spgemm_forward_records (halo records)", output=out)
     check_tensor(records, "records", torch.uint8)
     if records.numel() != g.num_cols * 5 * k:
         raise RuntimeError(f"records must hold num_cols = {g.num_cols} records of 5k bytes")
@@ -1222,6 +1309,7 @@ def spgemm_forward_records(g: MaxKGraph, records: torch.Tensor, k: int, dim_orig
 
 
 def spgemm_forward_multi(g: MaxKGraph, data, sel, values, dim_origin: int = 256, out=None):
+    fp32_only("the multi-relation forward", input_data=data, output=out)
     _check_cbsr(g, data, sel)
     k = data.shape[1]
     check_tensor(values, "values", torch.float32, dim=2)
@@ -1265,8 +1353,39 @@ def spgemm_forward_multi(g: MaxKGraph, data, sel, values, dim_origin: int = 256,
     return out
 
 
+_HALF_BWD_ALGOS = (_lib.MAXK_BWD_AUTO, _lib.MAXK_BWD_STAGED)
+
+
+def _backward_half(g: MaxKGraph, grad, sel, out, values, algo: int):
+    """Half-precision gradient rows: STAGED (AUTO means STAGED; nothing is timed).
+    fp32 staging rows and sums; a destination split over several segmented-sum
+    panels is summed from fp32 carry / owner rows and rounded once."""
+    if algo not in _HALF_BWD_ALGOS:
+        raise RuntimeError(f"the {_ALGO_NAMES.get(algo, algo)} backward is fp32 only: "
+                           f"{grad.dtype} gradients run MAXK_BWD_STAGED (or MAXK_BWD_AUTO, which "
+                           "resolves to it)")
+    if g.num_cols == 0:
+        return out
+    if g.num_rows == 0 or g.num_edges == 0:
+        return out.zero_()
+    L = _lib.load()
+    k = sel.shape[1]
+    dt = _lib.dtype_code(grad.dtype)
+    csc_pos, csc_indptr, csc_sched, CP = g.csc()
+    ws = g._workspace(("bwd", k), L.maxk_backward_workspace_bytes_t(_lib.MAXK_BWD_STAGED,
+                                                                     g.num_edges, k, CP, dt))
+    g.last_bwd_algo = "staged"
+    _lib.check(L.maxk_sspmm_backward_t(
+        _lib.MAXK_BWD_STAGED, g.bwd_sched.data_ptr(), g.bwd_num_panels, g.indptr.data_ptr(),
+        g.indices.data_ptr(), values.data_ptr(), grad.data_ptr(), dt, sel.data_ptr(), g.num_rows,
+        g.num_cols, g.num_edges, grad.shape[1], k, out.data_ptr(), dt, csc_pos.data_ptr(),
+        csc_sched.data_ptr(), CP, csc_indptr.data_ptr(), ws.data_ptr(), ws.numel(), _stream(out)),
+        "maxk_sspmm_backward_t")
+    return out
+
+
 def sspmm_backward(g: MaxKGraph, grad, sel, out=None, values=None, algo: int = _lib.MAXK_BWD_AUTO):
-    check_tensor(grad, "grad_output", torch.float32, dim=2)
+    check_feature(grad, "grad_output", dim=2)
     check_tensor(sel, "sparse_selector", torch.uint8, dim=2)
     if grad.shape[0] != g.num_rows or sel.shape[0] != g.num_cols:
         raise RuntimeError("grad_output rows must equal the graph's rows and sparse_selector "
@@ -1275,12 +1394,14 @@ def sspmm_backward(g: MaxKGraph, grad, sel, out=None, values=None, algo: int = _
     _on_device(g, grad_output=grad, sparse_selector=sel)
     values = _check_values(g, values)
     if out is None:
-        out = torch.empty((g.num_cols, k), dtype=torch.float32, device=g.device)
+        out = torch.empty((g.num_cols, k), dtype=grad.dtype, device=g.device)
     else:
-        check_tensor(out, "grad_input", torch.float32, dim=2)
+        check_feature(out, "grad_input", dim=2, like=grad)
         if tuple(out.shape) != (g.num_cols, k):
             raise RuntimeError("grad_input has the wrong shape")
         _on_device(g, grad_input=out)
+    if grad.dtype in HALF_DTYPES:
+        return _backward_half(g, grad, sel, out, values, algo)
     if g.num_cols == 0:
         return out
     if g.num_rows == 0:
@@ -1414,30 +1535,36 @@ _TOPK_ORDERS = {"column": _lib.MAXK_TOPK_ORDER_COLUMN, "value": _lib.MAXK_TOPK_O
 
 def topk_cbsr(x: torch.Tensor, k: int, order: str = "column", dense: bool = False,
               data: torch.Tensor | None = None, sel: torch.Tensor | None = None):
-    """CBSR of the row-wise top-k of x (fp32[V, h], h <= 256): (data fp32[V,k],
-    sel uint8[V,k]) with data[r, j] = x[r, sel[r, j]]; with dense=True also the
+    """CBSR of the row-wise top-k of x ([V, h] float32, float16 or bfloat16, h <= 256):
+    (data [V,k] in x's dtype, sel uint8[V,k]) with data[r, j] = x[r, sel[r, j]] (a half
+    x is ranked as x.float() would be and its entries are copied bit for bit); with dense=True also the
     MaxK forward (top-k kept, rest 0).  Replaces torch.topk in the reference's
     producers (direct_kernel_interface.py:79-83, spmm_bindings.cpp:163-184,
     utils/models.py:44-50).  order="column": ascending column; "value":
     descending value as torch.topk(sorted=True), ties to the lower column;
     "lane": column ranks interleaved for the forward kernel's lane layout.
     NaN ranks as the largest value."""
-    check_tensor(x, "input", torch.float32, dim=2)
+    check_feature(x, "input", dim=2)
     V, h = x.shape
     if not 1 <= k <= h or h > 256:
         raise RuntimeError(f"top-k needs 1 <= k <= dim <= 256 (k={k}, dim={h})")
     if order not in _TOPK_ORDERS:
         raise RuntimeError(f"order must be one of {sorted(_TOPK_ORDERS)}")
     if data is None:
-        data = torch.empty((V, k), dtype=torch.float32, device=x.device)
+        data = torch.empty((V, k), dtype=x.dtype, device=x.device)
     if sel is None:
         sel = torch.empty((V, k), dtype=torch.uint8, device=x.device)
-    check_tensor(data, "cbsr_data", torch.float32, dim=2)
+    check_feature(data, "cbsr_data", dim=2, like=x)
     check_tensor(sel, "cbsr_sel", torch.uint8, dim=2)
     if tuple(data.shape) != (V, k) or tuple(sel.shape) != (V, k):
         raise RuntimeError("cbsr_data / cbsr_sel must be [V, k]")
     out = torch.empty_like(x) if dense else None
     L = _lib.load()
+    if x.dtype in HALF_DTYPES:
+        _lib.check(L.maxk_topk_cbsr_t(x.data_ptr(), _lib.dtype_code(x.dtype), V, h, h, k,
+                                      _TOPK_ORDERS[order], data.data_ptr(), sel.data_ptr(),
+                                      _lib.ptr(out), _stream(x)), "maxk_topk_cbsr_t")
+        return (data, sel, out) if dense else (data, sel)
     _lib.check(L.maxk_topk_cbsr(x.data_ptr(), V, h, h, k, _TOPK_ORDERS[order], data.data_ptr(),
                                 sel.data_ptr(), _lib.ptr(out), _stream(x)), "maxk_topk_cbsr")
     return (data, sel, out) if dense else (data, sel)
@@ -1445,19 +1572,24 @@ def topk_cbsr(x: torch.Tensor, k: int, order: str = "column", dense: bool = Fals
 
 def cbsr_scatter(vals: torch.Tensor, sel: torch.Tensor, dim: int,
                  out: torch.Tensor | None = None) -> torch.Tensor:
-    """Dense fp32[V, dim] with out[r, sel[r, j]] = vals[r, j], 0 elsewhere: the
+    """Dense [V, dim] (vals' dtype) with out[r, sel[r, j]] = vals[r, j], 0 elsewhere: the
     sparse->dense gradient of SpGEMMFunction.backward (utils/models.py:136-141)."""
-    check_tensor(vals, "vals", torch.float32, dim=2)
+    check_feature(vals, "vals", dim=2)
     check_tensor(sel, "sparse_selector", torch.uint8, dim=2)
     if vals.shape != sel.shape:
         raise RuntimeError("vals and sparse_selector must have the same shape")
     V, k = sel.shape
     if out is None:
-        out = torch.empty((V, dim), dtype=torch.float32, device=vals.device)
-    check_tensor(out, "output", torch.float32, dim=2)
+        out = torch.empty((V, dim), dtype=vals.dtype, device=vals.device)
+    check_feature(out, "output", dim=2, like=vals)
     if tuple(out.shape) != (V, dim):
         raise RuntimeError("output must be [V, dim]")
     L = _lib.load()
+    if vals.dtype in HALF_DTYPES:
+        _lib.check(L.maxk_cbsr_scatter_t(vals.data_ptr(), _lib.dtype_code(vals.dtype),
+                                         sel.data_ptr(), V, k, dim, out.data_ptr(), _stream(vals)),
+                   "maxk_cbsr_scatter_t")
+        return out
     _lib.check(L.maxk_cbsr_scatter(vals.data_ptr(), sel.data_ptr(), V, k, dim, out.data_ptr(),
                                    _stream(vals)), "maxk_cbsr_scatter")
     return out
@@ -1465,15 +1597,20 @@ def cbsr_scatter(vals: torch.Tensor, sel: torch.Tensor, dim: int,
 
 def cbsr_mask(src: torch.Tensor, sel: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     """src masked to the selected columns (the MaxK backward, utils/models.py:52-59)."""
-    check_tensor(src, "grad_output", torch.float32, dim=2)
+    check_feature(src, "grad_output", dim=2)
     check_tensor(sel, "sparse_selector", torch.uint8, dim=2)
     V, dim = src.shape
     if sel.shape[0] != V:
         raise RuntimeError("sparse_selector rows must match grad_output rows")
     if out is None:
         out = torch.empty_like(src)
-    check_tensor(out, "output", torch.float32, dim=2)
+    check_feature(out, "output", dim=2, like=src)
     L = _lib.load()
+    if src.dtype in HALF_DTYPES:
+        _lib.check(L.maxk_cbsr_mask_t(src.data_ptr(), _lib.dtype_code(src.dtype), sel.data_ptr(), V,
+                                      sel.shape[1], dim, out.data_ptr(), _stream(src)),
+                   "maxk_cbsr_mask_t")
+        return out
     _lib.check(L.maxk_cbsr_mask(src.data_ptr(), sel.data_ptr(), V, sel.shape[1], dim,
                                 out.data_ptr(), _stream(src)), "maxk_cbsr_mask")
     return out

@@ -15,7 +15,7 @@ import time
 import torch
 
 from .graph_cache import graph_for
-from .ops import check_tensor, topk_cbsr
+from .ops import check_tensor, fp32_only, topk_cbsr
 
 
 def _sel_u8(sparse_selector):
@@ -32,6 +32,7 @@ class _SpmmBase:
         for t, n in ((indptr, "indptr"), (indices, "indices"), (values, "values"),
                      (input_features, "input_features"), (output_features, "output_features")):
             check_tensor(t, n)
+        fp32_only("spmm_kernels", input_features=input_features, output_features=output_features)
         self._graph_name = graph_name
         self._graph = graph_for(indptr, indices, values)
         self._vin, self._vout = input_features, output_features
@@ -41,6 +42,7 @@ class _SpmmBase:
     def update_input_output(self, input_features, output_features):
         check_tensor(input_features, "input_features")
         check_tensor(output_features, "output_features")
+        fp32_only("spmm_kernels", input_features=input_features, output_features=output_features)
         self._vin, self._vout = input_features, output_features
 
     def set_sparse_params(self, sparse_selector, maxk):
